@@ -18,6 +18,9 @@ per-kernel durations (HIP events on the launch stream, taken inside the library)
 cores.  Secondary: ``cg_iterations_per_s`` (the reference CG loop on the same
 problem, 50 iterations) and, for N > 1, ``cg_strong_iterations_per_s`` (the same 4096
 positions split over the ranks: strong scaling of the CG loop).
+
+``--dump-outputs DIR`` writes what the last timed step returned (``dump_outputs``): the
+inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -33,7 +36,7 @@ for _p in (ROOT, os.path.join(ROOT, "libtike-cufft_amd")):
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak bandwidth
 
 
 def parse():
@@ -53,7 +56,44 @@ def parse():
     ap.add_argument("--no-cfg3", action="store_true", help="skip the configs[2] secondary figures (4096 x 512^2, 4 modes)")
     ap.add_argument("--cfg3-iters", type=int, default=6)
     ap.add_argument("--no-shard", action="store_true", help="skip the configs[3] shard and configs[4] angle-streaming secondary figures")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/object.npy (the adjoint's "
+                         "object) and DIR/farplane.npy (the forward's farplane at a fixed, seeded sample of positions): "
+                         "float32, trailing (real, imag) axis, at most 64 MB in all.  The farplane is the same bits from run "
+                         "to run; the object, summed with float atomics, agrees to float32 rounding")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def workload(R, step, nprb, ngpu=1, rank=0):
+    """The seeded inputs of the timed step: common object covering the raster of all ranks (rank r owns raster rows
+    [rR, (r+1)R)), Gaussian probe, rank r's R x R positions.  Identical from run to run for the same arguments."""
+    from libtike.hipfft import synthetic as syn
+    nz, n = syn.object_size_for(R * ngpu, R, step, nprb)
+    psi_h = syn.random_object(nz, n, np.random.default_rng(1234))
+    prb_h = syn.gaussian_probe(nprb)
+    scan_h = syn.raster_scan(R, R, step, np.random.default_rng(1234 + 17 * rank), y0=float(rank * R * step))
+    return psi_h, prb_h, scan_h, nz, n
+
+
+def dump_index(n, budget, row_bytes):
+    """Rows of an [ntheta, n, ...] output that --dump-outputs writes: all of them if they fit ``budget`` bytes, else a
+    fixed, seeded, sorted sample of as many as fit (at least one)."""
+    k = max(1, min(n, budget // row_bytes))
+    return np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+
+
+def dump_outputs(path, g, upd):
+    """--dump-outputs: the farplane ``g`` and the object update ``upd`` one timed step returned, as float32 with a
+    trailing (real, imag) axis.  The object is written whole up to 16 MiB and the farplane up to 32 MiB (64 positions
+    of 256 x 256); beyond that, a seeded sample of object rows / positions (``dump_index``)."""
+    os.makedirs(path, exist_ok=True)
+    for name, x, budget in (("object", upd, 16 << 20), ("farplane", g, 32 << 20)):
+        idx = dump_index(x.shape[1], budget, x[:, :1].numel() * 8)
+        x = x if len(idx) == x.shape[1] else x[:, torch.as_tensor(idx, device=x.device)]
+        np.save(os.path.join(path, name + ".npy"), torch.view_as_real(x).cpu().numpy())
 
 
 def cfg3_figures(pt, syn, dev, iters):
@@ -370,13 +410,7 @@ def main():
 
     R, step, nprb, ndet = args.raster, args.step_px, args.nprb, args.ndet
     nscan = R * R
-    # common object covering the raster of all ranks (rank r owns raster rows [rR, (r+1)R))
-    nz, n = syn.object_size_for(R * ngpu, R, step, nprb)
-    rng = np.random.default_rng(1234)
-    psi_h = syn.random_object(nz, n, rng)
-    prb_h = syn.gaussian_probe(nprb)
-    rng_r = np.random.default_rng(1234 + 17 * rank)
-    scan_h = syn.raster_scan(R, R, step, rng_r, y0=float(rank * R * step))
+    psi_h, prb_h, scan_h, nz, n = workload(R, step, nprb, ngpu, rank)
     prob = {"psi": psi_h, "probe": prb_h, "scan": scan_h, "nz": nz, "n": n, "raster": R}
 
     dev = torch.device("cuda", local)
@@ -438,7 +472,7 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        upd = one_step()
     fence()
     elapsed = time.perf_counter() - t0
     if dist:
@@ -447,6 +481,8 @@ def main():
         elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / args.steps
     value = ngpu * nscan * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, g_buf, upd)     # before the loops below overwrite both buffers
 
     # The timed steps reuse the position order of the first call (the scan tensor is unchanged: option trust_order).
     # A caller whose positions change between calls pays the sort in both operators: same step, order forgotten

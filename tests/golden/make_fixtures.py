@@ -1,9 +1,9 @@
 """Convert the reference's test fixtures (DATA files of its own tests,
-``/root/reference/tests/model/*``) into one
-compressed ``.npz`` that can travel to the GPU box, where ``/root/reference``
-does not exist.  Values are copied bit for bit (float32); nothing is computed.
+``tests/model/*`` of a reference checkout) into one
+compressed ``.npz`` stored here, so that the tests need no reference checkout.
+Values are copied bit for bit (float32); nothing is computed.
 
-    python tests/golden/make_fixtures.py
+    python tests/golden/make_fixtures.py <reference checkout>/tests/model
 
 The TIFFs are 32-bit float images; ``probes_*.tiff`` hold 5 frames
 (``tests/test_modes.py:31-36`` reads them as ``[nmodes,128,128]``).
@@ -14,13 +14,12 @@ import sys
 import numpy as np
 from PIL import Image
 
-SRC = "/root/reference/tests/model"
 DST = os.path.join(os.path.dirname(os.path.abspath(__file__)),
                    "model_fixtures.npz")
 
 
-def read_tiff(name):
-    im = Image.open(os.path.join(SRC, name))
+def read_tiff(src, name):
+    im = Image.open(os.path.join(src, name))
     frames = []
     for k in range(getattr(im, "n_frames", 1)):
         im.seek(k)
@@ -28,15 +27,15 @@ def read_tiff(name):
     return frames[0] if len(frames) == 1 else np.stack(frames)
 
 
-def main():
+def main(src):
     out = {
-        "coords": np.load(os.path.join(SRC, "coords.npy")).astype(np.float32),
-        "prbamp": read_tiff("prbamp.tiff"),
-        "prbang": read_tiff("prbang.tiff"),
-        "initpsiamp": read_tiff("initpsiamp.tiff"),
-        "initpsiang": read_tiff("initpsiang.tiff"),
-        "probes_amp": read_tiff("probes_amp.tiff"),
-        "probes_ang": read_tiff("probes_ang.tiff"),
+        "coords": np.load(os.path.join(src, "coords.npy")).astype(np.float32),
+        "prbamp": read_tiff(src, "prbamp.tiff"),
+        "prbang": read_tiff(src, "prbang.tiff"),
+        "initpsiamp": read_tiff(src, "initpsiamp.tiff"),
+        "initpsiang": read_tiff(src, "initpsiang.tiff"),
+        "probes_amp": read_tiff(src, "probes_amp.tiff"),
+        "probes_ang": read_tiff(src, "probes_ang.tiff"),
     }
     for k, v in out.items():
         print(k, v.dtype, v.shape, float(v.min()), float(v.max()))
@@ -45,4 +44,6 @@ def main():
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    if len(sys.argv) != 2:
+        sys.exit(__doc__)
+    sys.exit(main(sys.argv[1]))

@@ -79,10 +79,10 @@ def test_zoom_window_kernel_is_low_rank():
     assert P._zoom_real_factors(256, 150, 1, "cpu") is None      # a window that is not low rank
 
 
-def test_fft_core_on_host():
+def test_fft_core_on_host(tmp_path):
     """Stockham index math of csrc/fft_core.hpp for every plan (16..2048, both
     directions) emulated thread by thread on the host against a naive DFT."""
-    exe = "/tmp/pty_host_check"
+    exe = str(tmp_path / "pty_host_check")
     subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2",
                     os.path.join(CSRC, "host_check.cpp"), "-o", exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True)
