@@ -68,6 +68,7 @@ int ptycho_free(ptycho_handle h);
 int ptycho_destroy(ptycho_handle h);
 /* read-only size fields: which = 0 ptheta, 1 nz, 2 n, 3 nscan, 4 ndet, 5 nprb;
  * 100: positions per launch pair of the adjoint (option "chunk"), 101: option "window";
+ * 102: 1 if a measured-pixel mask is set (ptycho_set_mask), else 0;
  * 200 + slot (slot < 16): 1 if CG work slot `slot` (one farplane, ptheta * nscan * ndet^2 * 8 bytes) is allocated. */
 long long ptycho_get(ptycho_handle h, int which);
 
@@ -106,6 +107,17 @@ int ptycho_fft2(ptycho_handle h, void* dst, const void* src, size_t nbatch,
  *                                                                             (ptycho.py:383-393,253-281) */
 int ptycho_cg_fwd_cols(ptycho_handle h, int slot, const void* f, const void* scan,
                        const void* prb, void* stream);
+/* Measured-pixel mask of the CG stages.  mask: DEVICE array of ndet * ndet bytes in the layout of data (un-fftshifted,
+ * DC at [0, 0]), nonzero = measured; NULL clears the mask.  The handle packs it into a buffer of its own (freed by
+ * ptycho_free; the caller's array may go once this returns) and checks it on the host (one synchronisation of `stream`).
+ * While a mask is set, every ptycho_cg_* stage that reads data -- stats, project, project_multi, linesearch,
+ * intensity_modes (sums), linesearch_modes and the native object / probe / line-search stages built on them -- sums
+ * over measured pixels only: data, the intensity and the line-search terms count as 0 at an unmeasured pixel, whatever
+ * data holds there (NaN and Inf included), and the projected residual is 0 there.  An all-ones mask gives the bits of
+ * no mask.  ptycho_fwd / adj / fft2, ptycho_cg_cross / argmax / zoom do not use it.
+ * PTYCHO_ERR_ARG: a mask with no measured pixel (a / b would be 0 / 0), or a detector size without a Stockham plan
+ * (those sizes have no fused CG stages). */
+int ptycho_set_mask(ptycho_handle h, const void* mask, void* stream);
 int ptycho_cg_stats(ptycho_handle h, int slot, const void* data, double* sums, void* stream);
 int ptycho_cg_project(ptycho_handle h, int src_slot, int dst_slot, const void* data,
                       const double* ab, double* cost, void* stream);

@@ -222,6 +222,8 @@ struct RowFusedArgs {
     // EP_CROSS: if set, best[0 .. nbest) <- 0 for the arg-max column pass that follows (saves its zero fill)
     unsigned long long* best_zero;
     int nbest;
+    // MASK variant: measured-pixel words packed by k_pack_mask<N> (one word per row and thread, bit m = pixel j0 + m T)
+    const unsigned* mask;
 };
 
 // ---- line_search_sqr's accept / shrink loop on the device (ptycho.py:253-281) -------------------------------
@@ -288,9 +290,36 @@ constexpr int fused_min_waves() {
 template <>
 constexpr int fused_min_waves<256, EP_STATS>() { return 4;   // 0.527 -> 0.505 ms (PROJECT at three waves spills: 1.03 -> 1.31)
 }
+// ---- measured-pixel mask (ptycho_set_mask) ---------------------------------------------------------------------
+// Packed in the order the fused row stages own the pixels after the last row-FFT step: thread j0 of row y holds the
+// pixels x = j0 + m T, m < E, so word y T + j0 carries them in bits 0 .. E-1 (E <= 28).  A thread reads one coalesced
+// word per row; the whole mask is N T words (16 KiB at 256^2, 64 KiB at 512^2) and stays in L2.
+template <int N>
+__global__ __launch_bounds__(256) void k_pack_mask(const unsigned char* __restrict__ m, unsigned* __restrict__ out,
+                                                   unsigned* __restrict__ nmeasured) {
+    using P = Plan<N>;
+    static_assert(P::E <= 32, "one mask word per thread and row");
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w >= N * P::T) return;
+    const int y = w / P::T, j0 = w % P::T;
+    unsigned bits = 0u;
+    for (int k = 0; k < P::E; ++k) bits |= (m[y * N + j0 + k * P::T] != 0 ? 1u : 0u) << k;
+    out[w] = bits;
+    if (bits) atomicAdd(nmeasured, (unsigned)__popc(bits));
+}
+// bit k of a mask word as an all-ones / zero word
+__device__ __forceinline__ unsigned mask_bit(unsigned w, int k) { return (unsigned)((int)(w << (31 - k)) >> 31); }
+__device__ __forceinline__ float and_f(float x, unsigned m) { return __uint_as_float(__float_as_uint(x) & m); }
+__device__ __forceinline__ c32 and_c(c32 x, unsigned m) { return c32{and_f(x.x, m), and_f(x.y, m)}; }
+
 // FW: the launch covers the full width (xa = 0, xb = N -- the probe fills the detector): no column predicate, loads unconditional
-template <int N, int EP, bool FW = false>
+// MASK: pixels outside the measured-pixel mask (a.mask) are left out of every sum.  The data value, the intensity and the
+// line-search terms are ANDed with the pixel's mask word as they are loaded or formed (no multiply by zero: unmeasured data
+// may hold NaN / Inf), the projected residual is ANDed before its inverse DFT.  An all-ones mask gives the bits of MASK =
+// false: no sum is reordered.
+template <int N, int EP, bool FW = false, bool MASK = false>
 __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(const RowFusedArgs a) {
+    static_assert(!MASK || EP != EP_CROSS, "the cross stage does not read data");
     using P = Plan<N>;
     using F = Fft<P, -1>;
     using L = RowLds<N>;
@@ -415,11 +444,14 @@ __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(
         // masked loads exploded to 581-1116 spilled registers and 441 ms.  profiles/r04/cfg3_experiments.txt.)
         fwd_row(v, g1);
         float d[E];
+        unsigned mw = 0u;   // MASK: this thread's measured-pixel word of row r % N (read in load_data)
         auto load_data = [&]() {
+            if constexpr (MASK) mw = a.mask[(unsigned)(r % N) * T + j0];
 #pragma unroll
             for (int m = 0; m < E; ++m) {
                 if constexpr (FW) d[m] = load_masked(a.data + boff + (fNs + (unsigned)(j0 + m * T)), rowm);
                 else d[m] = ok ? __builtin_nontemporal_load(a.data + boff + (fN + (unsigned)(j0 + m * T))) : 0.0f;
+                if constexpr (MASK) d[m] = and_f(d[m], mask_bit(mw, m));
             }
         };
         if (EP == EP_STATS || EP == EP_PROJECT) load_data();
@@ -469,7 +501,8 @@ __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(
         if (EP == EP_STATS) {
 #pragma unroll
             for (int m = 0; m < E; ++m) {
-                const float I = g1[m].x * g1[m].x + g1[m].y * g1[m].y;
+                float I = g1[m].x * g1[m].x + g1[m].y * g1[m].y;
+                if constexpr (MASK) I = and_f(I, mask_bit(mw, m));
                 acc[0] += fsqrt(I * d[m]);
                 acc[1] += I;
             }
@@ -495,6 +528,7 @@ __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(
                 load_data();
 #pragma unroll
                 for (int m = 0; m < E; ++m) {
+                    if constexpr (MASK) I[m] = and_f(I[m], mask_bit(mw, m));
                     acc[0] += fsqrt(I[m] * d[m]);
                     acc[1] += I[m];
                 }
@@ -506,11 +540,13 @@ __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(
             for (int m = 0; m < E; ++m) {
                 // single mode: S comes from the unscaled probe -> I' = |g|^2 s^2, fpsi = (g s)(1/s');
                 // multi mode: S comes from the rescaled probe and I is the summed intensity array
-                const float I = a.inten ? (ok ? a.inten[boff + (fN + (unsigned)(j0 + m * T))] : 0.0f) * s2
-                                        : (g1[m].x * g1[m].x + g1[m].y * g1[m].y) * s2;
+                float I = a.inten ? (ok ? a.inten[boff + (fN + (unsigned)(j0 + m * T))] : 0.0f) * s2
+                                  : (g1[m].x * g1[m].x + g1[m].y * g1[m].y) * s2;
+                if constexpr (MASK) I = and_f(I, mask_bit(mw, m));
                 const c32 fp = (a.inten && !a.first) ? g1[m] * sinv : (g1[m] * s) * sinv;
                 const float sd = fsqrt(d[m]), sI = fsqrt(I);
                 rr[m] = fp - (fp * sd) * frcp(sI + 1e-32f);
+                if constexpr (MASK) rr[m] = and_c(rr[m], mask_bit(mw, m));
                 const float df = sI - sd;
                 acc[0] += ok ? df * df : 0.0f;
             }
@@ -569,6 +605,13 @@ __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(
 #pragma unroll
                 for (int m = 0; m < E; ++m) p1[m] = ok ? a.inten[boff + (fN + (unsigned)(j0 + m * T))] : 0.0f;
             }
+            if constexpr (MASK) {
+#pragma unroll
+                for (int m = 0; m < E; ++m) {
+                    const unsigned mb = mask_bit(mw, m);
+                    p1[m] = and_f(p1[m], mb); p2[m] = and_f(p2[m], mb); p3[m] = and_f(p3[m], mb);
+                }
+            }
 #pragma unroll
             for (int m = 0; m < E; m += 2) {
                 const c32 q1 = c32{p1[m], p1[m + 1]}, q2 = c32{p2[m], p2[m + 1]}, q3 = c32{p3[m], p3[m + 1]};
@@ -606,10 +649,14 @@ __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(
             }
 #pragma unroll
             for (int m = 0; m < E; m += 2) {
-                const c32 ta = g1[m] * s, tb = g1[m + 1] * s;
+                c32 ta = g1[m] * s, tb = g1[m + 1] * s, ua = g2[m], ub = g2[m + 1];
+                if constexpr (MASK) {   // t1 = s g1, t2 = g2 of an unmeasured pixel are 0: p1 = p2 = p3 = 0 exactly
+                    const unsigned ma = mask_bit(mw, m), mb = mask_bit(mw, m + 1);
+                    ta = and_c(ta, ma); ua = and_c(ua, ma); tb = and_c(tb, mb); ub = and_c(ub, mb);
+                }
                 const c32 p1 = c32{ta.x * ta.x + ta.y * ta.y, tb.x * tb.x + tb.y * tb.y};
-                const c32 p2 = c32{g2[m].x * g2[m].x + g2[m].y * g2[m].y, g2[m + 1].x * g2[m + 1].x + g2[m + 1].y * g2[m + 1].y};
-                const c32 p3 = c32{2.0f * (ta.x * g2[m].x + ta.y * g2[m].y), 2.0f * (tb.x * g2[m + 1].x + tb.y * g2[m + 1].y)};
+                const c32 p2 = c32{ua.x * ua.x + ua.y * ua.y, ub.x * ub.x + ub.y * ub.y};
+                const c32 p3 = c32{2.0f * (ta.x * ua.x + ta.y * ua.y), 2.0f * (tb.x * ub.x + tb.y * ub.y)};
                 const c32 sd = c32{fsqrt(d[m]), fsqrt(d[m + 1])};
                 c32 df = c32{fsqrt(fabsf(p1.x)), fsqrt(fabsf(p1.y))} - sd;
                 acc2[kMaxCand] += df * df;

@@ -121,6 +121,8 @@ struct ptycho_handle_s {
     int native_order = 0;     // 1: the native CG stages are running and track scan themselves (ptycho_cg_obj_finish re-sorts
                               // after it moved the positions); cleared by ptycho_fwd / ptycho_adj, whose callers own trust_order
     const float* order_scan = nullptr;   // scan pointer the current order was computed from
+    unsigned* mask = nullptr;       // measured-pixel mask of the CG stages that read data (ptycho_set_mask), nullptr: none
+    unsigned* mask_buf = nullptr;   // ... its buffer (k_pack_mask layout + a count word), kept across masks, freed by ptycho_free
 #ifdef PTY_STAMPS
     unsigned long long* stamps = nullptr;   // diagnostic build: 24 words (forward column pass, object adjoint column pass)
 #endif
@@ -743,6 +745,19 @@ int do_cg_rows(ptycho_handle h, RowFusedArgs a, hipStream_t st) {
         ProfSpan ps(h, (EP == EP_STATS || EP == EP_STATS_M) ? K_ROWS_STATS : EP == EP_PROJECT ? K_ROWS_PROJECT : (EP == EP_LINESEARCH || EP == EP_LINESEARCH_M) ? K_ROWS_LINESEARCH : K_ROWS_CROSS, st);
         // full-width variant (unconditional masked loads): line search 0.292 -> 0.252 ms per pass, cross 1.65 -> 1.61, statistics 0.540 -> 0.517
         // (rocprofv3, 4096 x 256^2), projection 0.98 -> 1.01 (kept on the predicated variant); 8.39 -> 8.33 ms per CG iteration by the wall clock
+        if constexpr (EP != EP_CROSS) {
+            if (h->mask) {   // measured-pixel mask set: the MASK variants (same launch shape)
+                a.mask = h->mask;
+                if constexpr (EP != EP_PROJECT) {
+                    if (a.xa == 0 && a.xb == N) hipLaunchKernelGGL((k_rows_fused<N, EP, true, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
+                    else hipLaunchKernelGGL((k_rows_fused<N, EP, false, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
+                } else {
+                    hipLaunchKernelGGL((k_rows_fused<N, EP, false, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
+                }
+                HIP_TRY(hipGetLastError());
+                return PTYCHO_OK;
+            }
+        }
         if (a.xa == 0 && a.xb == N && EP != EP_PROJECT) hipLaunchKernelGGL((k_rows_fused<N, EP, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
         else hipLaunchKernelGGL((k_rows_fused<N, EP, false>), dim3((unsigned)grid), dim3(256), 0, st, a);
     }
@@ -931,6 +946,32 @@ int sort_positions(ptycho_handle h, const float* scan, hipStream_t st) {
     return PTYCHO_OK;
 }
 
+// ptycho_set_mask: pack ndet^2 bytes (nonzero = measured) into h->mask and count the measured pixels
+template <int N>
+int pack_mask(ptycho_handle h, const unsigned char* m, hipStream_t st) {
+    constexpr int W = N * Plan<N>::T;
+    static_assert(W <= N * N / 12, "mask buffer size");
+    unsigned* cnt = h->mask_buf + W;
+    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned), st));
+    hipLaunchKernelGGL((k_pack_mask<N>), dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, m, h->mask_buf, cnt);
+    HIP_TRY(hipGetLastError());
+    unsigned n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, cnt, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n == 0) return fail(PTYCHO_ERR_ARG, "mask has no measured pixel (a / b would be 0 / 0)");
+    h->mask = h->mask_buf;
+    return PTYCHO_OK;
+}
+
+int set_mask_dispatch(ptycho_handle h, const unsigned char* m, hipStream_t st) {
+    h->mask = nullptr;
+    if (!h->mask_buf) {   // every plan has N T <= N^2 / 12 words; + the count word
+        const size_t n = (size_t)h->ge.ndet * h->ge.ndet;
+        HIP_TRY(hipMalloc((void**)&h->mask_buf, (n / 12 + 1) * sizeof(unsigned)));
+    }
+    PTY_DISPATCH(h->ge.ndet, (pack_mask<NN>(h, m, st)));
+}
+
 int alloc_sort(ptycho_handle h) {
     const size_t total = (size_t)h->ge.ptheta * h->ge.nscan;
     const size_t nwords = total + (total + 255) / 256;
@@ -942,6 +983,8 @@ int alloc_sort(ptycho_handle h) {
 
 void release(ptycho_handle h) {
     if (h->slot_maxw) { (void)hipFree(h->slot_maxw); h->slot_maxw = nullptr; }
+    if (h->mask_buf) { (void)hipFree(h->mask_buf); h->mask_buf = nullptr; }
+    h->mask = nullptr;
     void* ptrs[] = {h->det_acc, (void*)h->fold.part, (void*)h->fold.ticket, h->det_words, h->bs_chirp, h->bs_hfilt, h->table, h->scratch, h->order, h->sort_counts, h->zoom_phase, h->prbp, h->reg_ip, h->reg_best, h->reg_shifts};
     h->det_acc = nullptr; h->fold.part = nullptr; h->fold.ticket = nullptr; h->det_words = nullptr; h->zoom_phase = nullptr; h->prbp = nullptr; h->bs_chirp = nullptr; h->bs_hfilt = nullptr; h->reg_ip = nullptr; h->reg_best = nullptr; h->reg_shifts = nullptr;
     for (auto& w : h->work) { if (w) (void)hipFree(w); w = nullptr; }
@@ -1092,6 +1135,7 @@ long long ptycho_get(ptycho_handle h, int which) {
         case 5: return h->ge.nprb;
         case 100: return h->chunk;
         case 101: return h->use_window;
+        case 102: return h->mask ? 1 : 0;   // measured-pixel mask set (ptycho_set_mask)?
         default:
             if (which >= 200 && which < 200 + ptycho_handle_s::kSlots) return h->work[which - 200] ? 1 : 0;   // CG work slot allocated?
             return -1;
@@ -1169,6 +1213,17 @@ int ptycho_set_option(ptycho_handle h, const char* name, long long value) {
         return PTYCHO_OK;
     }
     return fail(PTYCHO_ERR_ARG, std::string("unknown option ") + name);
+}
+
+int ptycho_set_mask(ptycho_handle h, const void* mask, void* stream) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (!mask) {   // clear (the buffer stays for the next mask)
+        h->mask = nullptr;
+        return PTYCHO_OK;
+    }
+    return set_mask_dispatch(h, static_cast<const unsigned char*>(mask), st);
 }
 
 int ptycho_profile(ptycho_handle h, int enable) {

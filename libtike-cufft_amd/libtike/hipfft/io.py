@@ -24,11 +24,14 @@ _ATTRS = ("detector_pixel_size", "detector_distance", "incident_wavelength", "ro
 class PtychoDataset:
     """One view: ``data`` float32 ``[nscan, ndet, ndet]`` un-fftshifted (DC at ``[0, 0]``, the layout the
     operators use), ``positions`` float32 ``[nscan, 2]`` in object pixels (``[:, 0]`` = row), ``probes``
-    complex64 ``[nmodes, nprb, nprb]`` -- ``PtychoDAO`` of ``test_rec_script.py:11-19``."""
+    complex64 ``[nmodes, nprb, nprb]`` -- ``PtychoDAO`` of ``test_rec_script.py:11-19``.  ``mask``: optional
+    measured-pixel mask ``[ndet, ndet]`` in the layout of ``data`` (nonzero = measured), ``None`` if the record has
+    none; ``solver_inputs`` hands it to the solver."""
 
-    def __init__(self, pid, data, positions, probes, rotation_angle=None):
+    def __init__(self, pid, data, positions, probes, rotation_angle=None, mask=None):
         self.pid, self.data, self.positions = pid, data, positions
         self.probes, self.rotation_angle = probes, rotation_angle
+        self.mask = mask
 
     @classmethod
     def from_record(cls, rec, pid=0, use_original_positions=False, swap_position_axes=True,
@@ -36,10 +39,19 @@ class PtychoDataset:
                     data_fftshift=True, view_dims=(2048, 2048), map_position_detector_pixel=1.0):
         """``rec``: mapping with ``data``, ``positions_0`` / ``positions_1``, ``initprobe`` / ``recprobe`` and
         the attributes ``detector_pixel_size, detector_distance, incident_wavelength, rotation_angle``.
-        Same steps, in the same order, as ``PtychoDAO.h5_reader`` (``test_rec_script.py:40-102``)."""
+        Same steps, in the same order, as ``PtychoDAO.h5_reader`` (``test_rec_script.py:40-102``).  An optional
+        ``mask`` member (one detector frame in the file's layout, nonzero = measured) gets the same ``fftshift``
+        as the data."""
         data = np.array(rec["data"], dtype=np.float32, order="C")
         if data_fftshift:                                   # :44-46 detector frames are stored centred
             data = np.fft.fftshift(data, axes=(1, 2))
+        mask = rec.get("mask")
+        if mask is not None:
+            mask = np.array(mask, order="C")
+            if mask.shape != data.shape[1:]:
+                raise ValueError("mask: shape %s != detector frame %s" % (mask.shape, data.shape[1:]))
+            if data_fftshift:
+                mask = np.fft.fftshift(mask)
         probes = np.array(rec["initprobe" if use_original_probes else "recprobe"], dtype=np.complex64, order="C")
         if swap_probe_axes:                                 # :66-69
             probes = np.array(probes.swapaxes(1, 2), order="C")
@@ -61,7 +73,7 @@ class PtychoDataset:
         positions = np.array(positions[ids], dtype=np.float32, order="C")
         data = np.ascontiguousarray(data[ids])              # :98-100
         angle = rec.get("rotation_angle")                   # None for a missing key OR a missing HDF5 attribute
-        return cls(pid, data, positions, probes, None if angle is None else float(angle))
+        return cls(pid, data, positions, probes, None if angle is None else float(angle), mask)
 
     @classmethod
     def from_npz(cls, path, pid=None, **kw):
@@ -78,7 +90,7 @@ class PtychoDataset:
             raise ImportError("PtychoDataset.from_h5 needs h5py; convert the file to .npz "
                               "(same member names) and use from_npz") from e
         with h5py.File(path, "r") as fid:
-            rec = {k: np.array(fid[k]) for k in ("data", "positions_0", "positions_1", "initprobe", "recprobe")
+            rec = {k: np.array(fid[k]) for k in ("data", "positions_0", "positions_1", "initprobe", "recprobe", "mask")
                    if k in fid}
             rec.update({k: fid.attrs.get(k) for k in _ATTRS})
         return cls.from_record(rec, _pid_of(path) if pid is None else pid, **kw)
@@ -93,7 +105,7 @@ def _pid_of(path):
 def solver_inputs(ds, view_dims, nmodes=1):
     """Arrays for ``CGPtychoSolver.run_batch`` from one view (``test_rec_script.py:181-212``): a leading
     angle axis of 1, a flat start object ``exp(-0.25i)`` of ``view + ndet`` pixels, the first ``nmodes``
-    probes scaled to max |.| = 1 and the data scaled by the same factor squared."""
+    probes scaled to max |.| = 1 and the data scaled by the same factor squared; plus ``mask`` if the view has one."""
     data = ds.data[None].astype(np.float32)
     scan = ds.positions[None].astype(np.float32)
     prb = ds.probes[None, :nmodes].astype(np.complex64)
@@ -102,8 +114,11 @@ def solver_inputs(ds, view_dims, nmodes=1):
     scale = np.amax(np.abs(prb))
     data = data / scale ** 2
     prb = prb / scale
-    return {"data": np.ascontiguousarray(data, np.float32), "psi": psi.astype(np.complex64),
-            "scan": scan, "probe": np.ascontiguousarray(prb, np.complex64)}
+    out = {"data": np.ascontiguousarray(data, np.float32), "psi": psi.astype(np.complex64),
+           "scan": scan, "probe": np.ascontiguousarray(prb, np.complex64)}
+    if getattr(ds, "mask", None) is not None:
+        out["mask"] = ds.mask
+    return out
 
 
 def save_result_npz(path, pid, psi, probe, rotation_angle=None):

@@ -1086,18 +1086,53 @@ class CGPtychoSolver(PtychoHIP):
                 warnings.warn("Line search failed for conjugate gradient.")
         return {"psi": psi, "probe": probe}
 
+    def _stockham_size(self):
+        """The fused CG stages run on the detector sizes that have a Stockham plan of their own (csrc/fft_core.hpp): powers
+        of two and 48, 80, 96, 112, 192 (112 = the reference's own crop, tests/test_fsc.py:115-120); any other size: Bluestein
+        operators + the statement-by-statement loop of ``run``."""
+        return (self.ndet >= 16 and (self.ndet & (self.ndet - 1)) == 0) or self.ndet in (48, 80, 96, 112, 192)
+
+    def _mask_operand(self, mask, device):
+        """``mask`` (NumPy array or tensor, any dtype, nonzero = measured) -> uint8 ``[ndet, ndet]`` on ``device``."""
+        if mask is None:
+            return None
+        m = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask))
+        if tuple(m.shape) != (self.ndet, self.ndet):
+            raise ValueError("mask: shape %s != expected %s" % (tuple(m.shape), (self.ndet, self.ndet)))
+        m = m != 0
+        if not bool(m.any()):
+            raise ValueError("mask has no measured pixel (the probe rescale a / b would be 0 / 0)")
+        return m.to(device=device, dtype=torch.uint8).contiguous()
+
     def run(self, data, psi, scan, probe, piter, model="gaussian",
-            recover_prb=False, ortho_prb=False):
+            recover_prb=False, ortho_prb=False, mask=None):
         """Conjugate gradients for ptychography (``ptycho.py:283-488``).
 
         ``probe`` and ``scan`` are updated in place, like in the reference.
+
+        ``mask``: measured-pixel mask, shape ``[ndet, ndet]`` in the layout of ``data`` (un-fftshifted, DC at
+        ``[0, 0]``); any nonzero value means "measured".  A bool / integer / float NumPy array or tensor; the same mask
+        applies to every position and angle.  With a mask every sum over detector pixels runs over the measured pixels
+        only: the probe rescale ``a = sum sqrt(I d)``, ``b = sum I``, the gaussian cost ``sum (sqrt I - sqrt d)^2`` (the
+        logged cost and every line-search trial), and the object and probe residuals are exactly 0 at unmeasured pixels.
+        What ``data`` holds at an unmeasured pixel never matters (NaN and Inf included), and an all-ones mask gives the
+        bits of ``mask=None``.  The position correction does not read ``data`` and is unchanged.  ``ValueError`` for a
+        mask of the wrong shape or one with no measured pixel.
         """
         assert probe.ndim == 4, "probe needs 4 dimensions, not %d" % probe.ndim
+        mask = self._mask_operand(mask, data.device)
+        if mask is None:
+            return self._run(data, psi, scan, probe, piter, model, recover_prb, None)
+        try:
+            if self._stockham_size():       # the fused / native loops read it from the handle
+                nat.check(nat.set_mask(self._h, _ptr(mask), _stream()))
+            return self._run(data, psi, scan, probe, piter, model, recover_prb, mask.bool())
+        finally:
+            nat.check(nat.set_mask(self._h, None, None))
+
+    def _run(self, data, psi, scan, probe, piter, model, recover_prb, mask):
         nmodes = probe.shape[1]
-        # the fused CG stages run on the detector sizes that have a Stockham plan of their own (csrc/fft_core.hpp): powers
-        # of two and 48, 80, 96, 112, 192 (112 = the reference's own crop, tests/test_fsc.py:115-120); any other size: Bluestein
-        # operators + the statement-by-statement loop below
-        pow2 = (self.ndet >= 16 and (self.ndet & (self.ndet - 1)) == 0) or self.ndet in (48, 80, 96, 112, 192)
+        pow2 = self._stockham_size()
         # several modes: the compact slot layout runs its line search over position ranges, which needs the windowed
         # column pass (ndet <= 512); larger detectors take the statement-by-statement loop
         if self.fused and model == "gaussian" and pow2 and nmodes <= 8 and (nmodes == 1 or self.ndet <= 512):
@@ -1120,8 +1155,17 @@ class CGPtychoSolver(PtychoHIP):
                 if det:
                     nat.check(nat.set_option(self._h, b"deterministic", 0))
         nscan_total = self._nscan_total()
+        if mask is not None:
+            # measured pixels only: data, the intensities, the line-search terms and the residuals are selected to 0
+            # elsewhere (a select, not a product: unmeasured data may be NaN / Inf)
+            zero = torch.zeros((), dtype=data.dtype, device=data.device)
+            data = torch.where(mask, data, zero)
+            keep = lambda x: torch.where(mask, x, torch.zeros((), dtype=x.dtype, device=x.device))  # noqa: E731
+        else:
+            keep = lambda x: x  # noqa: E731
 
         def minf(fpsi):
+            fpsi = keep(fpsi)
             if model == "gaussian":
                 f = torch.sum((torch.sqrt(torch.abs(fpsi)) - torch.sqrt(data)) ** 2)
             elif model == "poisson":
@@ -1132,7 +1176,7 @@ class CGPtychoSolver(PtychoHIP):
             acc = torch.zeros_like(data)
             for k in range(nmodes):
                 acc += torch.abs(self.fwd(obj, scan, probe[:, k])) ** 2
-            return acc
+            return keep(acc)
 
         dprb = dpsi = gradprb0 = gradpsi0 = 0
         if self.verbose:
@@ -1153,12 +1197,12 @@ class CGPtychoSolver(PtychoHIP):
                 for k in range(nmodes):
                     fpsi = self.fwd(psi, scan, probe[:, k]) * (b / a)
                     gradpsi += self.adj(
-                        fpsi - torch.sqrt(data) * fpsi / (torch.sqrt(absfpsi) + 1e-32),
+                        keep(fpsi - torch.sqrt(data) * fpsi / (torch.sqrt(absfpsi) + 1e-32)),
                         scan, probe[:, k]) / (torch.max(torch.abs(probe[:, k])) ** 2)
             elif model == "poisson":
                 for k in range(nmodes):
                     gradpsi += self.adj(
-                        fpsi - data * fpsi / (absfpsi + 1e-32),    # noqa: F821 (reference bug kept)
+                        keep(fpsi - data * fpsi / (absfpsi + 1e-32)),    # noqa: F821 (reference bug kept)
                         scan, probe[:, k]) / (torch.max(torch.abs(probe[:, k])) ** 2)
             self._allreduce(gradpsi)
             # Dai-Yuan direction
@@ -1198,12 +1242,12 @@ class CGPtychoSolver(PtychoHIP):
                     absfprb = intensity(psi)
                     if model == "gaussian":
                         g = self.adj_probe(
-                            fprb - torch.sqrt(data) * fprb / (torch.sqrt(absfprb) + 1e-32),
+                            keep(fprb - torch.sqrt(data) * fprb / (torch.sqrt(absfprb) + 1e-32)),
                             scan, psi)
                         self._allreduce(g)
                         gradprb[:, m] = g / torch.max(torch.abs(psi)) ** 2 / nscan_total * nmodes
                     elif model == "poisson":
-                        g = self.adj_probe(fprb - data * fprb / (absfprb + 1e-32), scan, psi)
+                        g = self.adj_probe(keep(fprb - data * fprb / (absfprb + 1e-32)), scan, psi)
                         self._allreduce(g)
                         gradprb[:, m] = g / torch.max(torch.abs(psi)) ** 2 / nscan_total
                     if i == 0:
