@@ -69,6 +69,7 @@ int ptycho_destroy(ptycho_handle h);
 /* read-only size fields: which = 0 ptheta, 1 nz, 2 n, 3 nscan, 4 ndet, 5 nprb;
  * 100: positions per launch pair of the adjoint (option "chunk"), 101: option "window";
  * 102: 1 if a measured-pixel mask is set (ptycho_set_mask), else 0;
+ * 103: option "model" (0 gaussian, 1 poisson_ml);
  * 200 + slot (slot < 16): 1 if CG work slot `slot` (one farplane, ptheta * nscan * ndet^2 * 8 bytes) is allocated. */
 long long ptycho_get(ptycho_handle h, int which);
 
@@ -299,6 +300,13 @@ int ptycho_cg_cross_dev(ptycho_handle h, int slot1, int slot2, const double* gam
  * g for the scale (none after ptycho_cg_project, which leaves max |slot| on the device); needs the windowed kernels
  * (powers of two up to 512, or any other size with nprb <= ~1000); default 0: float atomics, as kernels.cu:73-80,92-93);
  * "compact_modes" (M = number of probe modes: compact slot layout + chunk-major position order, see above; 0 = slot pairs);
+ * "model" (likelihood of every stage that prices or projects against data: 0 = gaussian [default], 1 = poisson_ml; any
+ * other value PTYCHO_ERR_ARG).  With 1, ptycho_cg_project / project_multi and the projections of the native object and
+ * probe stages form the residual fpsi - d fpsi / (I' + 1e-32) and the cost sum I' - d ln(I' + 1e-32), and every
+ * line-search pass (ptycho_cg_linesearch, _modes, _chunk, ls_obj_chunk, ls_prb_pass and the native searches) prices
+ * sum |x| - d ln(|x| + 1e-32) for x = p1 + y^2 p2 + y p3.  The statistics of the probe rescale (a, b), the cross stage
+ * and the operators do not depend on it.  The probe gradient of poisson_ml is not multiplied by the number of modes:
+ * pass nmodes = 1 to ptycho_cg_prb_dir;
  * "defer_finish", "ls_fused_decide" (native CG stages on one GPU, see above; default 0);
  * "release_scratch" (any value: frees the adjoint's intermediate, which the fused CG stages never use; ptycho_adj re-allocates it);
  * "release_work" (value = slot: frees that CG work slot; the next stage that writes the slot allocates it again.  The native

@@ -160,11 +160,30 @@ __global__ __launch_bounds__(256) void k_rows_split(const RowArgs a) {
 //   EP_LINESEARCH t1 = s g1, t2 = g2: p1,p2,p3 (ptycho.py:383-391) and the cost
 //                 sum (sqrt|p1 + y^2 p2 + y p3| - sqrt d)^2 for y = gamma0 * 2^-j, j < ncand,
 //                 plus f(p1) -- every trial of line_search_sqr in one pass (ptycho.py:253-281)
+// The Poisson likelihood (MODEL = MODEL_POISSON_ML, option "model" = 1) changes the three data stages only:
+//   EP_PROJECT    r = fpsi - d fpsi / (I' + 1e-32), cost += I' - d ln(I' + 1e-32)
+//   EP_LINESEARCH every trial term is |x| - d ln(|x| + 1e-32) - (d - d ln(d + 1e-32)) instead of (sqrt|x| - sqrt d)^2
+//                 (the subtracted constant of the pixel cancels in every comparison; the logged cost is PROJECT's)
 // ---------------------------------------------------------------------------
-// v_sqrt_f32 / v_rcp_f32 (1 ulp).  The correctly rounded sqrtf()/division expand to ~15
-// instructions each; the line search evaluates 17 square roots per farplane element.
+// v_sqrt_f32 / v_rcp_f32 / v_log_f32 (1 ulp).  The correctly rounded sqrtf()/division/logf() expand to ~15
+// instructions each; the line search evaluates 17 square roots (or logarithms) per farplane element.
 __device__ __forceinline__ float fsqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ float flog2(float x) { return __builtin_amdgcn_logf(x); }
+constexpr float kLn2 = 0.693147180559945309f;
+enum CgModel { MODEL_GAUSSIAN = 0, MODEL_POISSON_ML = 1 };   // option "model" (ptycho_set_option)
+// Poisson line-search term of two detector pixels, |x| - d ln(|x| + 1e-32) - c with dl = d ln 2: one v_log_f32 per pixel
+// where the gaussian term (sqrt|x| - sqrt d)^2 has one v_sqrt_f32 (the two issue alike).  c = d - d ln(d + 1e-32) is
+// the term's value at x = d, a constant of the pixel: it cancels in every f(trial) > f(p1) comparison and keeps the
+// float32 partial sums near the size of the cost differences instead of sum d ln d (plain sums took other line-search
+// decisions than the float64 reference from the second iteration on)
+__device__ __forceinline__ c32 pml_shift(const c32 d, const c32 dl) {
+    return d - dl * c32{flog2(d.x + 1e-32f), flog2(d.y + 1e-32f)};
+}
+__device__ __forceinline__ c32 pml_term(const c32 x, const c32 dl, const c32 c) {
+    const c32 ax = c32{fabsf(x.x), fabsf(x.y)};
+    return (ax - c) - dl * c32{flog2(ax.x + 1e-32f), flog2(ax.y + 1e-32f)};
+}
 
 // An unconditional global load whose value is masked afterwards (m = all ones or zero, made opaque by the caller so that the
 // AND does not turn back into a select).  `pred ? load(p) : zero` puts every request into a branch of its own
@@ -317,9 +336,13 @@ __device__ __forceinline__ c32 and_c(c32 x, unsigned m) { return c32{and_f(x.x, 
 // line-search terms are ANDed with the pixel's mask word as they are loaded or formed (no multiply by zero: unmeasured data
 // may hold NaN / Inf), the projected residual is ANDed before its inverse DFT.  An all-ones mask gives the bits of MASK =
 // false: no sum is reordered.
-template <int N, int EP, bool FW = false, bool MASK = false>
+// MODEL: the likelihood of the data stages (CgModel).  MODEL_POISSON_ML exists for EP_PROJECT and the two line searches
+// only; the statistics of the probe rescale and the cross stage are the same for every model.
+template <int N, int EP, bool FW = false, bool MASK = false, int MODEL = MODEL_GAUSSIAN>
 __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(const RowFusedArgs a) {
     static_assert(!MASK || EP != EP_CROSS, "the cross stage does not read data");
+    constexpr bool PML = MODEL == MODEL_POISSON_ML;
+    static_assert(!PML || EP == EP_PROJECT || EP == EP_LINESEARCH || EP == EP_LINESEARCH_M, "model-independent stage");
     using P = Plan<N>;
     using F = Fft<P, -1>;
     using L = RowLds<N>;
@@ -544,11 +567,19 @@ __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(
                                   : (g1[m].x * g1[m].x + g1[m].y * g1[m].y) * s2;
                 if constexpr (MASK) I = and_f(I, mask_bit(mw, m));
                 const c32 fp = (a.inten && !a.first) ? g1[m] * sinv : (g1[m] * s) * sinv;
-                const float sd = fsqrt(d[m]), sI = fsqrt(I);
-                rr[m] = fp - (fp * sd) * frcp(sI + 1e-32f);
-                if constexpr (MASK) rr[m] = and_c(rr[m], mask_bit(mw, m));
-                const float df = sI - sd;
-                acc[0] += ok ? df * df : 0.0f;
+                if constexpr (PML) {
+                    // unbounded where I' -> 0 with d > 0 (|r| up to ~d / (2 sqrt(1e-32))): maxword below is the max of
+                    // the row actually stored, so the deterministic adjoint's fixed point follows it
+                    rr[m] = fp - (fp * d[m]) * frcp(I + 1e-32f);
+                    if constexpr (MASK) rr[m] = and_c(rr[m], mask_bit(mw, m));
+                    acc[0] += ok ? I - (d[m] * kLn2) * flog2(I + 1e-32f) : 0.0f;
+                } else {
+                    const float sd = fsqrt(d[m]), sI = fsqrt(I);
+                    rr[m] = fp - (fp * sd) * frcp(sI + 1e-32f);
+                    if constexpr (MASK) rr[m] = and_c(rr[m], mask_bit(mw, m));
+                    const float df = sI - sd;
+                    acc[0] += ok ? df * df : 0.0f;
+                }
             }
             // inverse DFT over x of the projected row, same twiddle registers (conjugated)
             F::from_natural(rr, v);
@@ -615,6 +646,22 @@ __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(
 #pragma unroll
             for (int m = 0; m < E; m += 2) {
                 const c32 q1 = c32{p1[m], p1[m + 1]}, q2 = c32{p2[m], p2[m + 1]}, q3 = c32{p3[m], p3[m + 1]};
+                if constexpr (PML) {
+                    const c32 dd = c32{d[m], d[m + 1]}, dl = dd * kLn2, c = pml_shift(dd, dl);
+                    acc2[kMaxCand] += pml_term(q1, dl, c);
+                    float gam = gam_first;
+#pragma unroll
+                    for (int j0c = 0; j0c < kMaxCand; j0c += 4) {
+                        if (j0c < ncand) {
+#pragma unroll
+                            for (int j = j0c; j < j0c + 4; ++j) {
+                                acc2[j] += pml_term(q1 + q2 * (gam * gam) + q3 * gam, dl, c);
+                                gam *= 0.5f;
+                            }
+                        }
+                    }
+                    continue;
+                }
                 const c32 sd = c32{fsqrt(d[m]), fsqrt(d[m + 1])};
                 c32 df = c32{fsqrt(fabsf(q1.x)), fsqrt(fabsf(q1.y))} - sd;
                 acc2[kMaxCand] += df * df;
@@ -657,6 +704,22 @@ __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(
                 const c32 p1 = c32{ta.x * ta.x + ta.y * ta.y, tb.x * tb.x + tb.y * tb.y};
                 const c32 p2 = c32{ua.x * ua.x + ua.y * ua.y, ub.x * ub.x + ub.y * ub.y};
                 const c32 p3 = c32{2.0f * (ta.x * ua.x + ta.y * ua.y), 2.0f * (tb.x * ub.x + tb.y * ub.y)};
+                if constexpr (PML) {
+                    const c32 dd = c32{d[m], d[m + 1]}, dl = dd * kLn2, c = pml_shift(dd, dl);
+                    acc2[kMaxCand] += pml_term(p1, dl, c);
+                    float gam = gfirst;
+#pragma unroll
+                    for (int j0c = 0; j0c < kMaxCand; j0c += 4) {
+                        if (j0c < ncand) {
+#pragma unroll
+                            for (int j = j0c; j < j0c + 4; ++j) {
+                                acc2[j] += pml_term(p1 + p2 * (gam * gam) + p3 * gam, dl, c);
+                                gam *= 0.5f;
+                            }
+                        }
+                    }
+                    continue;
+                }
                 const c32 sd = c32{fsqrt(d[m]), fsqrt(d[m + 1])};
                 c32 df = c32{fsqrt(fabsf(p1.x)), fsqrt(fabsf(p1.y))} - sd;
                 acc2[kMaxCand] += df * df;

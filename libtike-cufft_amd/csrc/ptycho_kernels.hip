@@ -123,6 +123,7 @@ struct ptycho_handle_s {
     const float* order_scan = nullptr;   // scan pointer the current order was computed from
     unsigned* mask = nullptr;       // measured-pixel mask of the CG stages that read data (ptycho_set_mask), nullptr: none
     unsigned* mask_buf = nullptr;   // ... its buffer (k_pack_mask layout + a count word), kept across masks, freed by ptycho_free
+    int model = MODEL_GAUSSIAN;     // likelihood of the CG stages that read data (option "model", CgModel)
 #ifdef PTY_STAMPS
     unsigned long long* stamps = nullptr;   // diagnostic build: 24 words (forward column pass, object adjoint column pass)
 #endif
@@ -721,6 +722,19 @@ int do_cg_adj_cols(ptycho_handle h, int slot, c32* f, const float* scan, c32* pr
     return rc;
 }
 
+// a fused row stage of a likelihood other than gaussian: the full-width variant where the launch covers the detector,
+// except for the projection (always the predicated one); nothing else is instantiated
+template <int N, int EP, bool MASK, int MODEL>
+void launch_rows_model(const RowFusedArgs& a, long long grid, hipStream_t st) {
+    if constexpr (EP != EP_PROJECT) {
+        if (a.xa == 0 && a.xb == N) {
+            hipLaunchKernelGGL((k_rows_fused<N, EP, true, MASK, MODEL>), dim3((unsigned)grid), dim3(256), 0, st, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_rows_fused<N, EP, false, MASK, MODEL>), dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
 template <int N, int EP>
 int do_cg_rows(ptycho_handle h, RowFusedArgs a, hipStream_t st) {
     constexpr int C = ColCfg<N>::C;
@@ -745,6 +759,15 @@ int do_cg_rows(ptycho_handle h, RowFusedArgs a, hipStream_t st) {
         ProfSpan ps(h, (EP == EP_STATS || EP == EP_STATS_M) ? K_ROWS_STATS : EP == EP_PROJECT ? K_ROWS_PROJECT : (EP == EP_LINESEARCH || EP == EP_LINESEARCH_M) ? K_ROWS_LINESEARCH : K_ROWS_CROSS, st);
         // full-width variant (unconditional masked loads): line search 0.292 -> 0.252 ms per pass, cross 1.65 -> 1.61, statistics 0.540 -> 0.517
         // (rocprofv3, 4096 x 256^2), projection 0.98 -> 1.01 (kept on the predicated variant); 8.39 -> 8.33 ms per CG iteration by the wall clock
+        if constexpr (EP == EP_PROJECT || EP == EP_LINESEARCH || EP == EP_LINESEARCH_M) {
+            if (h->model == MODEL_POISSON_ML) {   // Poisson likelihood: its own PROJECT / line-search variants (same launch shape)
+                a.mask = h->mask;
+                if (h->mask) launch_rows_model<N, EP, true, MODEL_POISSON_ML>(a, grid, st);
+                else launch_rows_model<N, EP, false, MODEL_POISSON_ML>(a, grid, st);
+                HIP_TRY(hipGetLastError());
+                return PTYCHO_OK;
+            }
+        }
         if constexpr (EP != EP_CROSS) {
             if (h->mask) {   // measured-pixel mask set: the MASK variants (same launch shape)
                 a.mask = h->mask;
@@ -1136,6 +1159,7 @@ long long ptycho_get(ptycho_handle h, int which) {
         case 100: return h->chunk;
         case 101: return h->use_window;
         case 102: return h->mask ? 1 : 0;   // measured-pixel mask set (ptycho_set_mask)?
+        case 103: return h->model;          // option "model": 0 gaussian, 1 poisson_ml
         default:
             if (which >= 200 && which < 200 + ptycho_handle_s::kSlots) return h->work[which - 200] ? 1 : 0;   // CG work slot allocated?
             return -1;
@@ -1172,6 +1196,11 @@ int ptycho_set_option(ptycho_handle h, const char* name, long long value) {
     }
     if (std::strcmp(name, "deterministic") == 0) {
         h->deterministic = value != 0;
+        return PTYCHO_OK;
+    }
+    if (std::strcmp(name, "model") == 0) {   // likelihood of the data stages: 0 gaussian, 1 Poisson maximum likelihood
+        if (value != MODEL_GAUSSIAN && value != MODEL_POISSON_ML) return fail(PTYCHO_ERR_ARG, "model must be 0 (gaussian) or 1 (poisson_ml)");
+        h->model = (int)value;
         return PTYCHO_OK;
     }
     if (std::strcmp(name, "compact_modes") == 0) {   // value = number of probe modes (0: slot pairs); also makes the order chunk-major

@@ -88,6 +88,9 @@ cg_obj_dir2 = _sig("ptycho_cg_obj_dir2", _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _
 set_mask = _sig("ptycho_set_mask", _i, _vp, _vp, _vp)
 #: ``get`` key: 1 if a measured-pixel mask is set on the handle
 GET_MASK = 102
+#: ``get`` key: option "model" of the CG stages that read data (MODEL_GAUSSIAN, MODEL_POISSON_ML)
+GET_MODEL = 103
+MODEL_GAUSSIAN, MODEL_POISSON_ML = 0, 1
 #: word offsets of the device-resident CG state (enum PTYCHO_ST_* in include/ptycho_hip.h)
 ST_A, ST_B, ST_COST, ST_COST2 = 0, 1, 2, 3
 ST_GAMMA_PSI, ST_GAMMA_PRB, ST_LS_FAILED, ST_HINT, ST_COSTS, ST_WORDS = 12, 13, 19, 20, 24, 160

@@ -709,7 +709,8 @@ class CGPtychoSolver(PtychoHIP):
         return _zoom_real_factors(self.ndet, 150, 100, self._device)
 
     def _run_native(self, data, psi, scan, probe, piter, recover_prb, zoom):
-        """``CGPtychoSolver.run`` (ptycho.py:283-488), one probe mode, gaussian model.  Same kernels and
+        """``CGPtychoSolver.run`` (ptycho.py:283-488), one probe mode, gaussian or poisson_ml model (option "model" of the
+        handle; the probe gradient's mode factor is 1 either way).  Same kernels and
         the same arithmetic as ``_run_fused``, but every scalar of the iteration (a, b, the Dai-Yuan
         sums, the line-search costs, the accepted step lengths) stays in a float64 state vector on the
         device and the line search is decided there (C ABI ``ptycho_cg_obj_* / prb_* / ls_next``): an
@@ -845,8 +846,8 @@ class CGPtychoSolver(PtychoHIP):
         return {"psi": psi, "probe": probe}
 
     def _run_fused(self, data, psi, scan, probe, piter, recover_prb):
-        """``CGPtychoSolver.run`` (ptycho.py:283-488) for one probe mode and the gaussian
-        model, with every farplane-sized elementwise stage fused into the DFT row pass
+        """``CGPtychoSolver.run`` (ptycho.py:283-488) for one probe mode and the gaussian or
+        poisson_ml model (option "model" of the handle), with every farplane-sized elementwise stage fused into the DFT row pass
         (C ABI ``ptycho_cg_*``).  Work buffer 0 holds the column pass of fwd(psi), which
         is shared by the intensity statistics, the gradient projection and the line
         search (the probe rescale ``a/b`` is linear and applied on the fly)."""
@@ -915,8 +916,9 @@ class CGPtychoSolver(PtychoHIP):
         return {"psi": psi, "probe": probe}
 
     # -- fused multi-mode gaussian loop ----------------------------------------------------
-    def _run_fused_multi(self, data, psi, scan, probe, piter, recover_prb):
-        """``CGPtychoSolver.run`` (ptycho.py:283-488), gaussian model, 2..8 incoherent probe modes.
+    def _run_fused_multi(self, data, psi, scan, probe, piter, recover_prb, model="gaussian"):
+        """``CGPtychoSolver.run`` (ptycho.py:283-488), gaussian or poisson_ml model (option "model" of the handle),
+        2..8 incoherent probe modes.
 
         Work slots (one farplane each), compact layout: slot k holds the column pass of
         fwd(psi, probe_k) -- made once per step for all modes by ONE launch that gathers the object
@@ -961,6 +963,7 @@ class CGPtychoSolver(PtychoHIP):
         B = M                        # shared: residual of one mode, then column passes of fwd(direction, .)
         vpp = ctypes.c_void_p * M
         passes = (1, 2, 4, 0)        # groups of 16 step lengths the NEXT pass prices (after the hint-sized first one)
+        prb_scale = M if model == "gaussian" else 1   # ptycho.py:431 (gaussian) / :441 (poisson)
 
         def mode_ptrs(modes):
             keep = [mode(modes, k) for k in range(M)]
@@ -1054,7 +1057,7 @@ class CGPtychoSolver(PtychoHIP):
                         g = torch.zeros((self.ptheta, self.nprb, self.nprb), dtype=torch.complex64, device=dev)
                         nat.check(nat.cg_adj_cols(self._h, B, _ptr(psi), _ptr(scan), _ptr(g), 1, _stream()))
                         self._allreduce(g)
-                        gradprb[:, m] = g / torch.max(torch.abs(psi)) ** 2 / nscan_total * M
+                        gradprb[:, m] = g / torch.max(torch.abs(psi)) ** 2 / nscan_total * prb_scale
                         if i == 0:
                             dprb[:, m] = -gradprb[:, m]
                         else:
@@ -1118,24 +1121,45 @@ class CGPtychoSolver(PtychoHIP):
         What ``data`` holds at an unmeasured pixel never matters (NaN and Inf included), and an all-ones mask gives the
         bits of ``mask=None``.  The position correction does not read ``data`` and is unchanged.  ``ValueError`` for a
         mask of the wrong shape or one with no measured pixel.
+
+        ``model``: the noise model of the cost.
+
+        * ``"gaussian"`` (default): least squares on amplitudes, ``f(I) = sum (sqrt|I| - sqrt d)^2``.
+        * ``"poisson_ml"``: Poisson maximum likelihood, ``f(I) = sum (|I| - d ln(|I| + 1e-32))``, for photon-counting
+          data at low dose.  It is the reference's ``"poisson"`` branch (``ptycho.py:308-313, 357-363, 436-441``) with
+          ``fpsi`` defined as in the gaussian branch: object residual ``fpsi - d fpsi / (I + 1e-32)`` per mode, probe
+          residual ``fprb - d fprb / (I + 1e-32)``, and a probe gradient that is not multiplied by the number of modes.
+          The probe rescale, the Dai-Yuan directions, ``line_search_sqr``, the position correction and the mask rules
+          are those of ``"gaussian"``.  The line-search trials are priced minus the per-pixel constant
+          ``d - d ln(d + 1e-32)``, which cancels in every comparison and keeps the float32 sums small; the logged
+          cost is ``f`` itself.
+        * ``"poisson"``: kept exactly as the reference has it, which reads ``fpsi`` before assigning it and so raises
+          ``UnboundLocalError`` on its first iteration.  Results of this solver are compared with the reference's, so
+          its branches are not changed; ``"poisson_ml"`` is the working form.
         """
         assert probe.ndim == 4, "probe needs 4 dimensions, not %d" % probe.ndim
         mask = self._mask_operand(mask, data.device)
-        if mask is None:
+        pml = model == "poisson_ml"
+        if mask is None and not pml:
             return self._run(data, psi, scan, probe, piter, model, recover_prb, None)
         try:
-            if self._stockham_size():       # the fused / native loops read it from the handle
+            if mask is not None and self._stockham_size():       # the fused / native loops read it from the handle
                 nat.check(nat.set_mask(self._h, _ptr(mask), _stream()))
-            return self._run(data, psi, scan, probe, piter, model, recover_prb, mask.bool())
+            if pml:
+                nat.check(nat.set_option(self._h, b"model", nat.MODEL_POISSON_ML))
+            return self._run(data, psi, scan, probe, piter, model, recover_prb, None if mask is None else mask.bool())
         finally:
-            nat.check(nat.set_mask(self._h, None, None))
+            if mask is not None:
+                nat.check(nat.set_mask(self._h, None, None))
+            if pml:
+                nat.check(nat.set_option(self._h, b"model", nat.MODEL_GAUSSIAN))
 
     def _run(self, data, psi, scan, probe, piter, model, recover_prb, mask):
         nmodes = probe.shape[1]
         pow2 = self._stockham_size()
         # several modes: the compact slot layout runs its line search over position ranges, which needs the windowed
         # column pass (ndet <= 512); larger detectors take the statement-by-statement loop
-        if self.fused and model == "gaussian" and pow2 and nmodes <= 8 and (nmodes == 1 or self.ndet <= 512):
+        if self.fused and model in ("gaussian", "poisson_ml") and pow2 and nmodes <= 8 and (nmodes == 1 or self.ndet <= 512):
             # The fused loops run on the deterministic adjoints unless told otherwise: with float atomics (the
             # reference's kernels.cu:73-80) two runs of the same problem take different line-search paths -- near a
             # flat start the accept / reject decisions sit on the last float32 digit of the cost -- and differ by
@@ -1150,7 +1174,8 @@ class CGPtychoSolver(PtychoHIP):
                     if zoom is not None:
                         return self._run_native(data, psi, scan, probe, piter, recover_prb, zoom)
                     return self._run_fused(data, psi, scan, probe, piter, recover_prb)
-                return self._run_fused_multi(data, psi, scan, probe, piter, recover_prb)   # one pair of work slots per mode
+                return self._run_fused_multi(data, psi, scan, probe, piter, recover_prb,   # one pair of work slots per mode
+                                             model)
             finally:
                 if det:
                     nat.check(nat.set_option(self._h, b"deterministic", 0))
@@ -1168,9 +1193,22 @@ class CGPtychoSolver(PtychoHIP):
             fpsi = keep(fpsi)
             if model == "gaussian":
                 f = torch.sum((torch.sqrt(torch.abs(fpsi)) - torch.sqrt(data)) ** 2)
-            elif model == "poisson":
+            elif model in ("poisson", "poisson_ml"):
                 f = torch.sum(torch.abs(fpsi) - data * torch.log(torch.abs(fpsi) + 1e-32))
             return self._allreduce(f)
+
+        if model == "poisson_ml":
+            # line-search trials: minus the per-pixel constant d - d ln(d + 1e-32) (the term's value at I = d), which
+            # cancels in every comparison of line_search_sqr and keeps the float32 sums near the size of the cost
+            # differences (as the fused kernels do); the logged cost stays minf
+            shift = data - data * torch.log(data + 1e-32)
+
+            def minf_ls(fpsi):
+                fpsi = keep(fpsi)
+                f = torch.sum(torch.abs(fpsi) - data * torch.log(torch.abs(fpsi) + 1e-32) - shift)
+                return self._allreduce(f)
+        else:
+            minf_ls = minf
 
         def intensity(obj):
             acc = torch.zeros_like(data)
@@ -1204,6 +1242,12 @@ class CGPtychoSolver(PtychoHIP):
                     gradpsi += self.adj(
                         keep(fpsi - data * fpsi / (absfpsi + 1e-32)),    # noqa: F821 (reference bug kept)
                         scan, probe[:, k]) / (torch.max(torch.abs(probe[:, k])) ** 2)
+            elif model == "poisson_ml":                   # the poisson branch with fpsi defined as above
+                for k in range(nmodes):
+                    fpsi = self.fwd(psi, scan, probe[:, k]) * (b / a)
+                    gradpsi += self.adj(
+                        keep(fpsi - data * fpsi / (absfpsi + 1e-32)),
+                        scan, probe[:, k]) / (torch.max(torch.abs(probe[:, k])) ** 2)
             self._allreduce(gradpsi)
             # Dai-Yuan direction
             if i == 0:
@@ -1220,7 +1264,7 @@ class CGPtychoSolver(PtychoHIP):
                 p1 += torch.abs(tmp1) ** 2
                 p2 += torch.abs(tmp2) ** 2
                 p3 += 2 * (tmp1.real * tmp2.real + tmp1.imag * tmp2.imag)
-            gammapsi = 0.5 * self.line_search_sqr(minf, p1, p2, p3)
+            gammapsi = 0.5 * self.line_search_sqr(minf_ls, p1, p2, p3)
 
             # position correction -- :398-403
             if i > 0:
@@ -1246,7 +1290,7 @@ class CGPtychoSolver(PtychoHIP):
                             scan, psi)
                         self._allreduce(g)
                         gradprb[:, m] = g / torch.max(torch.abs(psi)) ** 2 / nscan_total * nmodes
-                    elif model == "poisson":
+                    elif model in ("poisson", "poisson_ml"):
                         g = self.adj_probe(keep(fprb - data * fprb / (absfprb + 1e-32)), scan, psi)
                         self._allreduce(g)
                         gradprb[:, m] = g / torch.max(torch.abs(psi)) ** 2 / nscan_total
@@ -1263,7 +1307,7 @@ class CGPtychoSolver(PtychoHIP):
                     tmp2 = self.fwd(psi, scan, dprb[:, m])
                     p2 = torch.abs(tmp2) ** 2
                     p3 = 2 * (tmp1.real * tmp2.real + tmp1.imag * tmp2.imag)
-                    gammaprb = 0.5 * self.line_search_sqr(minf, p1, p2, p3, step_length=1)
+                    gammaprb = 0.5 * self.line_search_sqr(minf_ls, p1, p2, p3, step_length=1)
                     probe[:, m] = probe[:, m] + gammaprb * dprb[:, m]
 
             # check convergence -- :475-482 (cost of the start-of-iteration intensity)
