@@ -89,6 +89,20 @@ int ptycho_adj(ptycho_handle h, void* f, const void* g, const void* scan,
 int ptycho_fft2(ptycho_handle h, void* dst, const void* src, size_t nbatch,
                 int dir, void* stream);
 
+/* Orthogonal incoherent probe modes (CGPtychoSolver.run(..., ortho_prb=True); no counterpart in the reference, whose
+ * attempts are commented out at src/libtike/cufft/ptycho.py:414-419, 467-470).  Needs no handle.
+ * prb (and dprb, gradprb0 when not null): complex64 [ptheta][nmodes][npix], npix = nprb^2, rotated in place.  Per angle t,
+ * with P = [npix, nmodes] the modes of t: G = P^H P (float64, summed in a fixed order, bitwise reproducible),
+ * G = V diag(lambda) V^H by cyclic Jacobi in float64 with lambda descending (stable by index on exact ties) and every
+ * column of V scaled so that its component of largest magnitude (the lowest index on ties) is real and positive; then
+ * X <- X V for each of the three arrays.  The new modes are orthogonal, mode 0 the strongest, and sum |P_k|^2 per pixel is
+ * unchanged up to rounding.  Outputs: v_out complex128 [ptheta][nmodes][nmodes] (row k, column j = V_kj), powers float64
+ * [ptheta][nmodes] = lambda.  nmodes = 1: V = 1, only the power is computed.  Two launches on `stream`, no host
+ * synchronisation.  PTYCHO_ERR_ARG, before any HIP call, for nmodes outside [1, 16], a null prb / v_out / powers,
+ * npix == 0 or ptheta == 0. */
+int ptycho_orthogonalize_modes(void* prb, void* dprb, void* gradprb0, size_t ptheta, int nmodes, size_t npix,
+                               void* v_out, double* powers, void* stream);
+
 /* ---- fused CG-stage entry points ("plus fused CG-stage entry points") ----
  * The elementwise stages of CGPtychoSolver.run (src/libtike/cufft/ptycho.py:325-393) are
  * fused into the row pass of the DFT so that farplanes are never materialised.  The

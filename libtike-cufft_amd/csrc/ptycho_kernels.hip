@@ -31,6 +31,7 @@
 
 #include "../../include/ptycho_hip.h"
 #include "fft_core.hpp"
+#include "k_modes.hpp"
 
 using namespace pty;
 
@@ -2106,3 +2107,59 @@ int ptycho_cg_cross_dev(ptycho_handle h, int slot1, int slot2, const double* gam
 }
 
 }  // extern "C"
+
+// ---- orthogonal probe modes (k_modes.hpp): no handle ----
+template <int M>
+int do_orthogonalize_modes(c32* const* x, int narr, int ptheta, long long npix, double* v, double* powers, hipStream_t st) {
+    hipLaunchKernelGGL((k_mode_gram_eig<M>), dim3((unsigned)ptheta), dim3(256), 0, st, (const c32*)x[0], npix, v, powers);
+    HIP_TRY(hipGetLastError());
+    if constexpr (M > 1) {
+        ModeRotateArgs a{};
+        for (int i = 0; i < narr; ++i) a.x[i] = x[i];
+        a.v = v;
+        a.npix = npix;
+        a.blocks = (npix + 255) / 256;
+        a.ptheta = ptheta;
+        hipLaunchKernelGGL((k_mode_rotate<M>), dim3((unsigned)(a.blocks * ptheta * narr)), dim3(256), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return PTYCHO_OK;
+}
+
+extern "C" int ptycho_orthogonalize_modes(void* prb, void* dprb, void* gradprb0, size_t ptheta, int nmodes, size_t npix,
+                                          void* v_out, double* powers, void* stream) {
+    if (nmodes < 1 || nmodes > kOrthoMaxModes) return fail(PTYCHO_ERR_ARG, "nmodes must be in [1, 16]");
+    if (!prb) return fail(PTYCHO_ERR_ARG, "prb is null");
+    if (npix == 0) return fail(PTYCHO_ERR_ARG, "npix must be positive");
+    if (ptheta == 0) return fail(PTYCHO_ERR_ARG, "ptheta must be positive");
+    if (!v_out || !powers) return fail(PTYCHO_ERR_ARG, "v_out and powers must not be null");
+    const unsigned long long blocks = (npix + 255) / 256;
+    if (ptheta > (1u << 30) || npix > (1ull << 40) || blocks * ptheta * 3 > 0xffffffffull)
+        return fail(PTYCHO_ERR_ARG, "ptheta * npix too large for one launch");
+    c32* x[3] = {(c32*)prb, nullptr, nullptr};
+    int narr = 1;
+    if (dprb) x[narr++] = (c32*)dprb;
+    if (gradprb0) x[narr++] = (c32*)gradprb0;
+    const int pt = (int)ptheta;
+    const long long np = (long long)npix;
+    double* v = (double*)v_out;
+    hipStream_t st = (hipStream_t)stream;
+    switch (nmodes) {
+        case 1: return do_orthogonalize_modes<1>(x, narr, pt, np, v, powers, st);
+        case 2: return do_orthogonalize_modes<2>(x, narr, pt, np, v, powers, st);
+        case 3: return do_orthogonalize_modes<3>(x, narr, pt, np, v, powers, st);
+        case 4: return do_orthogonalize_modes<4>(x, narr, pt, np, v, powers, st);
+        case 5: return do_orthogonalize_modes<5>(x, narr, pt, np, v, powers, st);
+        case 6: return do_orthogonalize_modes<6>(x, narr, pt, np, v, powers, st);
+        case 7: return do_orthogonalize_modes<7>(x, narr, pt, np, v, powers, st);
+        case 8: return do_orthogonalize_modes<8>(x, narr, pt, np, v, powers, st);
+        case 9: return do_orthogonalize_modes<9>(x, narr, pt, np, v, powers, st);
+        case 10: return do_orthogonalize_modes<10>(x, narr, pt, np, v, powers, st);
+        case 11: return do_orthogonalize_modes<11>(x, narr, pt, np, v, powers, st);
+        case 12: return do_orthogonalize_modes<12>(x, narr, pt, np, v, powers, st);
+        case 13: return do_orthogonalize_modes<13>(x, narr, pt, np, v, powers, st);
+        case 14: return do_orthogonalize_modes<14>(x, narr, pt, np, v, powers, st);
+        case 15: return do_orthogonalize_modes<15>(x, narr, pt, np, v, powers, st);
+        default: return do_orthogonalize_modes<16>(x, narr, pt, np, v, powers, st);
+    }
+}

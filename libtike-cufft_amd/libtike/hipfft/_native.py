@@ -26,7 +26,7 @@ SYMBOLS = ("ptycho_create", "ptycho_free", "ptycho_destroy", "ptycho_get",
            "ptycho_cg_obj_finish", "ptycho_cg_prb_grad", "ptycho_cg_prb_dir", "ptycho_cg_prb_finish",
            "ptycho_cg_ls_begin", "ptycho_cg_ls_obj_chunk", "ptycho_cg_ls_prb_pass", "ptycho_cg_ls_decide",
            "ptycho_cg_cross_dev", "ptycho_cg_obj_begin2", "ptycho_cg_obj_dir2",
-           "ptycho_set_mask",
+           "ptycho_set_mask", "ptycho_orthogonalize_modes",
            "ptycho_last_error", "ptycho_version")
 
 if not os.path.exists(LIB_PATH):
@@ -86,6 +86,9 @@ cg_cross_dev = _sig("ptycho_cg_cross_dev", _i, _vp, _i, _i, _vp, _vp, _vp)
 cg_obj_begin2 = _sig("ptycho_cg_obj_begin2", _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 cg_obj_dir2 = _sig("ptycho_cg_obj_dir2", _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 set_mask = _sig("ptycho_set_mask", _i, _vp, _vp, _vp)
+#: orthogonal probe modes (no handle): prb, dprb, gradprb0, ptheta, nmodes, npix, v_out, powers, stream
+orthogonalize_modes = _sig("ptycho_orthogonalize_modes", _i, _vp, _vp, _vp, _sz, _i, _sz, _vp, _vp, _vp)
+ORTHO_MAX_MODES = 16
 #: ``get`` key: 1 if a measured-pixel mask is set on the handle
 GET_MASK = 102
 #: ``get`` key: option "model" of the CG stages that read data (MODEL_GAUSSIAN, MODEL_POISSON_ML)

@@ -21,7 +21,7 @@ import torch
 from . import _native as nat
 
 __all__ = ["PtychoHIP", "PtychoCuFFT", "CGPtychoSolver",
-           "register_translation_batch", "TorchArrayModule"]
+           "register_translation_batch", "orthogonalize_modes", "TorchArrayModule"]
 
 
 class TorchArrayModule:
@@ -568,6 +568,50 @@ def register_translation_batch(src_image, target_image, upsample_factor=1,
 
 
 # ---------------------------------------------------------------------------
+# orthogonal probe modes (C ABI ptycho_orthogonalize_modes, csrc/k_modes.hpp)
+# ---------------------------------------------------------------------------
+def orthogonalize_modes(probe, *companions):
+    """Make the incoherent modes of every angle orthogonal, strongest first, in place.
+
+    ``probe``: ``[ptheta, M, nprb, nprb]`` complex64 device tensor, 1 <= M <= 16.  Per angle, with ``P`` the
+    ``[nprb^2, M]`` matrix of its modes, ``G = P^H P`` (float64) is diagonalised, ``G = V diag(lam) V^H``, with ``lam``
+    descending (stable by index on exact ties) and each eigenvector scaled so that its component of largest magnitude
+    (the lowest index on ties) is real and positive; the modes become ``P V``.  Afterwards ``P^H P = diag(lam)`` up to
+    float32 rounding, ``sum(lam)`` equals ``sum_k |P_k|^2``, and the summed intensity ``sum_k |F(psi P_k)|^2`` of any
+    object is unchanged (the mixing is unitary).  ``companions`` (at most two tensors of the probe's shape, dtype and
+    device, e.g. a CG direction and a previous gradient) are rotated by the same ``V``.
+
+    Returns the powers ``lam``: a ``[ptheta, M]`` float64 device tensor (the mode occupancy is ``lam / lam.sum(1)``).
+    Two kernel launches on the current stream and no host synchronisation.
+    """
+    if not isinstance(probe, torch.Tensor) or probe.dtype != torch.complex64 or probe.ndim != 4 or not probe.is_cuda:
+        raise TypeError("probe must be a [ptheta, M, nprb, nprb] complex64 device tensor")
+    ptheta, nmodes = probe.shape[0], probe.shape[1]
+    if not 1 <= nmodes <= nat.ORTHO_MAX_MODES:
+        raise ValueError("orthogonalize_modes: %d modes, supported 1 .. %d" % (nmodes, nat.ORTHO_MAX_MODES))
+    if len(companions) > 2:
+        raise ValueError("orthogonalize_modes: at most two companions")
+    for c in companions:
+        if not isinstance(c, torch.Tensor) or c.shape != probe.shape or c.dtype != probe.dtype or c.device != probe.device:
+            raise ValueError("orthogonalize_modes: every companion needs the probe's shape, dtype and device")
+    npix = probe.shape[2] * probe.shape[3]
+    if ptheta == 0 or npix == 0:
+        return torch.zeros((ptheta, nmodes), dtype=torch.float64, device=probe.device)
+    tensors = (probe,) + tuple(companions)
+    work = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    with torch.cuda.device(probe.device):
+        powers = torch.empty((ptheta, nmodes), dtype=torch.float64, device=probe.device)
+        v = torch.empty((ptheta, nmodes, nmodes), dtype=torch.complex128, device=probe.device)
+        ptrs = [_ptr(w) for w in work] + [None] * (3 - len(work))
+        nat.check(nat.orthogonalize_modes(ptrs[0], ptrs[1], ptrs[2], ptheta, nmodes, npix, _ptr(v), _ptr(powers),
+                                          _stream()))
+    for t, w in zip(tensors, work):
+        if w is not t:
+            t.copy_(w)
+    return powers
+
+
+# ---------------------------------------------------------------------------
 # CG solver (ptycho.py:250-488)
 # ---------------------------------------------------------------------------
 class CGPtychoSolver(PtychoHIP):
@@ -916,7 +960,7 @@ class CGPtychoSolver(PtychoHIP):
         return {"psi": psi, "probe": probe}
 
     # -- fused multi-mode gaussian loop ----------------------------------------------------
-    def _run_fused_multi(self, data, psi, scan, probe, piter, recover_prb, model="gaussian"):
+    def _run_fused_multi(self, data, psi, scan, probe, piter, recover_prb, model="gaussian", ortho=False):
         """``CGPtychoSolver.run`` (ptycho.py:283-488), gaussian or poisson_ml model (option "model" of the handle),
         2..8 incoherent probe modes.
 
@@ -1004,6 +1048,7 @@ class CGPtychoSolver(PtychoHIP):
 
         dpsi = gradpsi0 = None
         dprb = gradprb0 = gradprb = None
+        powers = None
         if self.verbose:
             print("# congujate gradient parameters\n"
                   "iteration, step size object, step size probe, function min")
@@ -1069,6 +1114,8 @@ class CGPtychoSolver(PtychoHIP):
                         self._cg_fwd_cols(B, psi, scan, mode(dprb, m))
                         probe_line_search(m)                                        # -> state[GAMMA_PRB]
                         probe[:, m] = probe[:, m] + gprb_w.to(torch.float32) * dprb[:, m]
+                    if ortho:                                                       # ortho_prb
+                        powers = orthogonalize_modes(probe, dprb, gradprb0)
 
                 if i % self.log_every == 0:
                     snap = st[:nat.ST_LS_FAILED + 1].clone()
@@ -1087,7 +1134,10 @@ class CGPtychoSolver(PtychoHIP):
             st[nat.ST_LS_FAILED] = 0.0
             for _ in range(failed):
                 warnings.warn("Line search failed for conjugate gradient.")
-        return {"psi": psi, "probe": probe}
+        out = {"psi": psi, "probe": probe}
+        if powers is not None:
+            out["mode_powers"] = powers
+        return out
 
     def _stockham_size(self):
         """The fused CG stages run on the detector sizes that have a Stockham plan of their own (csrc/fft_core.hpp): powers
@@ -1136,25 +1186,42 @@ class CGPtychoSolver(PtychoHIP):
         * ``"poisson"``: kept exactly as the reference has it, which reads ``fpsi`` before assigning it and so raises
           ``UnboundLocalError`` on its first iteration.  Results of this solver are compared with the reference's, so
           its branches are not changed; ``"poisson_ml"`` is the working form.
+
+        ``ortho_prb``: keep the incoherent probe modes orthogonal (``orthogonalize_modes``).  At the end of every
+        iteration's probe step, after every mode has been updated, the modes of each angle are replaced by ``P V``,
+        with ``P^H P = V diag(lam) V^H``: mode 0 is then the strongest, ``P^H P = diag(lam)`` with ``lam`` descending
+        and ``sum(lam) = sum_k |P_k|^2``.  The summed intensity ``sum_k |F(psi P_k)|^2`` does not change under this
+        unitary mixing, so neither do the cost and the next iteration's rescale ``a / b`` (which keeps the modes
+        orthogonal).  The probe's CG direction and previous gradient are rotated by the same ``V``, so the per-mode
+        Dai-Yuan directions stay in the new basis.  The returned probe is orthogonal and sorted by power, and the
+        result gains ``"mode_powers"``: ``lam`` of the last orthogonalisation, a ``[ptheta, M]`` float64 device tensor.
+        Nothing happens with ``recover_prb=False`` (the reference placed it inside the probe step) or with one mode.
+        Works with ``mask=``, ``"gaussian"`` and ``"poisson_ml"``, ``run_batch`` and a process group (the probe is
+        replicated and the kernels are deterministic, so every rank computes the same ``V``).  ``ValueError`` for more
+        than 16 modes.
         """
         assert probe.ndim == 4, "probe needs 4 dimensions, not %d" % probe.ndim
+        ortho = bool(ortho_prb) and bool(recover_prb) and probe.shape[1] > 1
+        if ortho_prb and probe.shape[1] > nat.ORTHO_MAX_MODES:
+            raise ValueError("ortho_prb: %d probe modes, supported up to %d" % (probe.shape[1], nat.ORTHO_MAX_MODES))
         mask = self._mask_operand(mask, data.device)
         pml = model == "poisson_ml"
         if mask is None and not pml:
-            return self._run(data, psi, scan, probe, piter, model, recover_prb, None)
+            return self._run(data, psi, scan, probe, piter, model, recover_prb, None, ortho)
         try:
             if mask is not None and self._stockham_size():       # the fused / native loops read it from the handle
                 nat.check(nat.set_mask(self._h, _ptr(mask), _stream()))
             if pml:
                 nat.check(nat.set_option(self._h, b"model", nat.MODEL_POISSON_ML))
-            return self._run(data, psi, scan, probe, piter, model, recover_prb, None if mask is None else mask.bool())
+            return self._run(data, psi, scan, probe, piter, model, recover_prb, None if mask is None else mask.bool(),
+                             ortho)
         finally:
             if mask is not None:
                 nat.check(nat.set_mask(self._h, None, None))
             if pml:
                 nat.check(nat.set_option(self._h, b"model", nat.MODEL_GAUSSIAN))
 
-    def _run(self, data, psi, scan, probe, piter, model, recover_prb, mask):
+    def _run(self, data, psi, scan, probe, piter, model, recover_prb, mask, ortho=False):
         nmodes = probe.shape[1]
         pow2 = self._stockham_size()
         # several modes: the compact slot layout runs its line search over position ranges, which needs the windowed
@@ -1175,7 +1242,7 @@ class CGPtychoSolver(PtychoHIP):
                         return self._run_native(data, psi, scan, probe, piter, recover_prb, zoom)
                     return self._run_fused(data, psi, scan, probe, piter, recover_prb)
                 return self._run_fused_multi(data, psi, scan, probe, piter, recover_prb,   # one pair of work slots per mode
-                                             model)
+                                             model, ortho)
             finally:
                 if det:
                     nat.check(nat.set_option(self._h, b"deterministic", 0))
@@ -1217,6 +1284,7 @@ class CGPtychoSolver(PtychoHIP):
             return keep(acc)
 
         dprb = dpsi = gradprb0 = gradpsi0 = 0
+        powers = None
         if self.verbose:
             print("# congujate gradient parameters\n"
                   "iteration, step size object, step size probe, function min")
@@ -1309,6 +1377,8 @@ class CGPtychoSolver(PtychoHIP):
                     p3 = 2 * (tmp1.real * tmp2.real + tmp1.imag * tmp2.imag)
                     gammaprb = 0.5 * self.line_search_sqr(minf_ls, p1, p2, p3, step_length=1)
                     probe[:, m] = probe[:, m] + gammaprb * dprb[:, m]
+                if ortho:                       # ortho_prb
+                    powers = orthogonalize_modes(probe, dprb, gradprb0)
 
             # check convergence -- :475-482 (cost of the start-of-iteration intensity)
             if i % self.log_every == 0:
@@ -1316,4 +1386,7 @@ class CGPtychoSolver(PtychoHIP):
                 self.history.append((i, float(gammapsi), float(gammaprb), cost))
                 if self.verbose:
                     print("%4d, %.3e, %.3e, %.7e" % self.history[-1])
-        return {"psi": psi, "probe": probe}
+        out = {"psi": psi, "probe": probe}
+        if powers is not None:
+            out["mode_powers"] = powers
+        return out
