@@ -402,14 +402,33 @@ def test_profile_read_accepts_the_16_entry_arrays_of_earlier_headers(pt):
     from libtike.hipfft import _native as nat
     p, probe, ora, data = setup(1)
     D = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
+    GUARD = -7777
     with pt.PtychoCuFFT(p["nscan"], 32, 32, 1, p["nz"], p["n"]) as slv:
+        psi, scan, prb = D(p["psi"]), D(p["scan"]), D(probe[:, 0])
+
+        def read(n, size):
+            # arrays of `size` entries, the ones past n filled with guard words; n tells the library how many it may write
+            ms, cnt = (ctypes.c_double * size)(*([float(GUARD)] * size)), (ctypes.c_longlong * size)(*([GUARD] * size))
+            nat.check(nat.profile_read(slv._h, ms, cnt, n))
+            assert list(cnt[n:]) == [GUARD] * (size - n) and list(ms[n:]) == [float(GUARD)] * (size - n), "overrun"
+            return list(cnt[:n])
+
         slv.profile(True)
-        slv.fwd(D(p["psi"]), D(p["scan"]), D(probe[:, 0]))
-        ms, cnt = (ctypes.c_double * 16)(), (ctypes.c_longlong * 16)()
-        nat.check(nat.profile_read(slv._h, ms, cnt, 16))          # ids 16 / 17 (the tile kernels of ndet <= 128) are dropped
-        assert sum(cnt) == 0 or all(c >= 0 for c in cnt)
+        # two-pass forward (an id < 16: k_cols<FWD> = 0): counted by the 16-entry read
+        slv.set_tile(False)
+        slv.fwd(psi, scan, prb)
+        cnt = read(16, 20)
+        assert cnt[0] >= 1, cnt
+        # one-launch tile forward (id 16): counted by an 18-entry read, absent from a 16-entry read, nothing written past it
+        slv.set_tile(True)
+        slv.fwd(psi, scan, prb)
+        cnt = read(18, 20)
+        assert cnt[16] == 1, cnt
+        slv.fwd(psi, scan, prb)
+        cnt = read(16, 20)
+        assert cnt[:16] == [0] * 16, cnt
         with pytest.raises(nat.PtychoHipError):
-            nat.check(nat.profile_read(slv._h, ms, cnt, 15))
+            nat.check(nat.profile_read(slv._h, (ctypes.c_double * 16)(), (ctypes.c_longlong * 16)(), 15))
 
 
 def test_pending_deferred_gradient_is_guarded(pt):
