@@ -103,6 +103,21 @@ int ptycho_fft2(ptycho_handle h, void* dst, const void* src, size_t nbatch,
 int ptycho_orthogonalize_modes(void* prb, void* dprb, void* gradprb0, size_t ptheta, int nmodes, size_t npix,
                                void* v_out, double* powers, void* stream);
 
+/* Fourier ring correlation (no handle; libtike.hipfft.frc).  Both calls are one launch on `stream`, no host
+ * synchronisation; s (the crop side) must be in [16, 1024] or 2048, ptheta in [1, 32767].
+ *   ptycho_frc_prepare  out (complex64 [2][ptheta][s][s]) <- the crops [.., y0:y0+s, x0:x0+s] of a, then of b (complex64
+ *                       [ptheta][nz][n] each), times window[y] * window[x] (float32 [s]; NULL: no window)
+ *   ptycho_frc_rings    sums (float64 [ptheta][s/2+1][5]) <- per angle and ring k = round(|f|) <= s/2 of the spectra in
+ *                       spec (complex64 [2][ptheta][s][s], A then B): {Re C, Im C, PA, PB, n} with C = sum A conj(B'),
+ *                       PA = sum |A|^2, PB = sum |B|^2, n the pixel count, B' = B exp(-2 pi i (fy dy + fx dx) / s) with
+ *                       (dy, dx) = shift[angle] (float64 [ptheta][2] on the device; NULL: no shift).  Fixed summation
+ *                       order, no atomics: the same inputs give the same bits.
+ * PTYCHO_ERR_ARG, before any HIP call, for a null out / a / b / sums / spec, an unsupported s or ptheta, or a crop
+ * outside the image. */
+int ptycho_frc_prepare(void* out, const void* a, const void* b, size_t ptheta, size_t nz, size_t n, size_t y0, size_t x0,
+                       size_t s, const float* window, void* stream);
+int ptycho_frc_rings(double* sums, const void* spec, size_t ptheta, size_t s, const double* shift, void* stream);
+
 /* ---- fused CG-stage entry points ("plus fused CG-stage entry points") ----
  * The elementwise stages of CGPtychoSolver.run (src/libtike/cufft/ptycho.py:325-393) are
  * fused into the row pass of the DFT so that farplanes are never materialised.  The

@@ -32,6 +32,7 @@
 #include "../../include/ptycho_hip.h"
 #include "fft_core.hpp"
 #include "k_modes.hpp"
+#include "k_frc.hpp"
 
 using namespace pty;
 
@@ -2162,4 +2163,31 @@ extern "C" int ptycho_orthogonalize_modes(void* prb, void* dprb, void* gradprb0,
         case 15: return do_orthogonalize_modes<15>(x, narr, pt, np, v, powers, st);
         default: return do_orthogonalize_modes<16>(x, narr, pt, np, v, powers, st);
     }
+}
+
+// ---- Fourier ring correlation (k_frc.hpp, libtike.hipfft.frc) ------------------------------------------------------------
+extern "C" int ptycho_frc_prepare(void* out, const void* a, const void* b, size_t ptheta, size_t nz, size_t n, size_t y0,
+                                  size_t x0, size_t s, const float* window, void* stream) {
+    if (!out || !a || !b) return fail(PTYCHO_ERR_ARG, "out, a and b must not be null");
+    if (!frc_size_ok((long long)s)) return fail(PTYCHO_ERR_ARG, "s must be in [16, 1024] or 2048");
+    if (ptheta == 0 || ptheta > kFrcMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 32767]");
+    if (y0 > nz || s > nz - y0 || x0 > n || s > n - x0) return fail(PTYCHO_ERR_ARG, "the crop lies outside the image");
+    if (nz > (1ull << 32) || n > (1ull << 32)) return fail(PTYCHO_ERR_ARG, "image too large");
+    const dim3 grid((unsigned)((s + 255) / 256), (unsigned)s, (unsigned)(2 * ptheta));
+    hipLaunchKernelGGL(k_frc_prepare, grid, dim3(256), 0, (hipStream_t)stream, (c32*)out, (const c32*)a, (const c32*)b,
+                       (int)ptheta, (long long)nz, (long long)n, (long long)y0, (long long)x0, (int)s, window);
+    HIP_TRY(hipGetLastError());
+    return PTYCHO_OK;
+}
+
+extern "C" int ptycho_frc_rings(double* sums, const void* spec, size_t ptheta, size_t s, const double* shift,
+                                void* stream) {
+    if (!sums || !spec) return fail(PTYCHO_ERR_ARG, "sums and spec must not be null");
+    if (!frc_size_ok((long long)s)) return fail(PTYCHO_ERR_ARG, "s must be in [16, 1024] or 2048");
+    if (ptheta == 0 || ptheta > kFrcMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 32767]");
+    const dim3 grid((unsigned)frc_rings((int)s), (unsigned)ptheta);
+    hipLaunchKernelGGL(k_frc_rings, grid, dim3(kFrcThreads), 0, (hipStream_t)stream, sums, (const c32*)spec, (int)ptheta,
+                       (int)s, shift);
+    HIP_TRY(hipGetLastError());
+    return PTYCHO_OK;
 }

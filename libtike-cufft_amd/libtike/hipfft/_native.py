@@ -27,6 +27,7 @@ SYMBOLS = ("ptycho_create", "ptycho_free", "ptycho_destroy", "ptycho_get",
            "ptycho_cg_ls_begin", "ptycho_cg_ls_obj_chunk", "ptycho_cg_ls_prb_pass", "ptycho_cg_ls_decide",
            "ptycho_cg_cross_dev", "ptycho_cg_obj_begin2", "ptycho_cg_obj_dir2",
            "ptycho_set_mask", "ptycho_orthogonalize_modes",
+           "ptycho_frc_prepare", "ptycho_frc_rings",
            "ptycho_last_error", "ptycho_version")
 
 if not os.path.exists(LIB_PATH):
@@ -89,6 +90,10 @@ set_mask = _sig("ptycho_set_mask", _i, _vp, _vp, _vp)
 #: orthogonal probe modes (no handle): prb, dprb, gradprb0, ptheta, nmodes, npix, v_out, powers, stream
 orthogonalize_modes = _sig("ptycho_orthogonalize_modes", _i, _vp, _vp, _vp, _sz, _i, _sz, _vp, _vp, _vp)
 ORTHO_MAX_MODES = 16
+#: Fourier ring correlation (no handle): out, a, b, ptheta, nz, n, y0, x0, s, window, stream
+frc_prepare = _sig("ptycho_frc_prepare", _i, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _vp)
+#: sums, spec, ptheta, s, shift, stream
+frc_rings = _sig("ptycho_frc_rings", _i, _vp, _vp, _sz, _sz, _vp, _vp)
 #: ``get`` key: 1 if a measured-pixel mask is set on the handle
 GET_MASK = 102
 #: ``get`` key: option "model" of the CG stages that read data (MODEL_GAUSSIAN, MODEL_POISSON_ML)
