@@ -671,6 +671,49 @@ class CGPtychoSolver(PtychoHIP):
             step_length *= step_shrink
         return step_length
 
+    # -- host glue shared by the CG drivers -------------------------------------------------
+    def _state(self, dev):
+        """The float64 state vector of the native stages, made once per device with both line-search hints at 14.  The
+        two step lengths are zeroed: a run without probe recovery logs step 0, as the reference prints."""
+        st = self.__dict__.get("_cg_state")
+        if st is None or st.device != dev:
+            st = self._cg_state = torch.zeros(nat.ST_WORDS, dtype=torch.float64, device=dev)
+            st[nat.ST_HINT:nat.ST_HINT + 2] = 14.0
+        st[nat.ST_GAMMA_PSI:nat.ST_GAMMA_PRB + 1] = 0.0
+        return st
+
+    def _ones(self, probe):
+        """The all-ones probe of the position correction (ptycho.py:399), made once per shape and device."""
+        ones = self.__dict__.get("_ones_probe")
+        if ones is None or ones.shape != probe[:, 0].shape or ones.device != probe.device:
+            ones = self._ones_probe = torch.ones_like(probe[:, 0])
+        return ones
+
+    def _log_header(self):
+        if self.verbose:
+            print("# congujate gradient parameters\n"
+                  "iteration, step size object, step size probe, function min")
+
+    def _log(self, i, gammapsi, gammaprb, cost):
+        self.history.append((i, gammapsi, gammaprb, cost))
+        if self.verbose:
+            print("%4d, %.3e, %.3e, %.7e" % self.history[-1])
+
+    def _log_state(self, i, st):
+        """``_log`` from a snapshot of the device state vector (the cost summed over the ranks)."""
+        snap = st[:nat.ST_LS_FAILED + 1].clone()
+        self._allreduce(snap[nat.ST_COST:nat.ST_COST + 1])
+        snap = snap.cpu()
+        self._log(i, float(snap[nat.ST_GAMMA_PSI]), float(snap[nat.ST_GAMMA_PRB]),
+                  float(snap[nat.ST_COST].to(torch.float32)))
+
+    def _replay_ls_failures(self, st):
+        """The device-resident loops count failed line searches; warn once per failure, as the reference does."""
+        failed = int(st[nat.ST_LS_FAILED].item())
+        if failed:
+            st[nat.ST_LS_FAILED] = 0.0
+            for _ in range(failed):
+                warnings.warn("Line search failed for conjugate gradient.")
 
     # -- fused single-mode gaussian loop -------------------------------------------------
     def _cg_fwd_cols(self, slot, obj, scan, prb):
@@ -681,9 +724,7 @@ class CGPtychoSolver(PtychoHIP):
         """Shifts of ptycho.py:398-403.  Fused form (one angle): column passes of
         fwd(psi, 1) and fwd(dpsi, 1), one row pass that forms u1 conj(u1 + gamma u2) and its
         inverse row DFT, one column pass with a fused arg-max; then the zoomed DFT."""
-        ones = self.__dict__.get("_ones_probe")
-        if ones is None or ones.shape != probe[:, 0].shape or ones.device != probe.device:
-            ones = self._ones_probe = torch.ones_like(probe[:, 0])
+        ones = self._ones(probe)
         if not (self.fused and self.ptheta == 1):
             g32 = gammapsi.to(torch.float32) if isinstance(gammapsi, torch.Tensor) else gammapsi
             tmp1 = self.fwd(psi, scan, ones)[0]
@@ -767,16 +808,10 @@ class CGPtychoSolver(PtychoHIP):
         self._operand(scan, torch.float32, (self.ptheta, self.nscan, 2), "scan")
         assert probe.dtype == torch.complex64 and probe.is_contiguous() and scan.is_contiguous()
         vt, lz, nc = zoom
-        st = self.__dict__.get("_cg_state")
-        if st is None or st.device != dev:
-            st = self._cg_state = torch.zeros(nat.ST_WORDS, dtype=torch.float64, device=dev)
-            st[nat.ST_HINT:nat.ST_HINT + 2] = 14.0
-        st[nat.ST_GAMMA_PSI:nat.ST_GAMMA_PRB + 1] = 0.0       # a run without probe recovery logs step 0, as the reference prints
+        st = self._state(dev)
         h = self._h
         sp, costs = _ptr(st), st[nat.ST_COSTS:nat.ST_COSTS + nat.ST_NCOSTS]
-        ones = self.__dict__.get("_ones_probe")
-        if ones is None or ones.shape != probe[:, 0].shape or ones.device != dev:
-            ones = self._ones_probe = torch.ones_like(probe[:, 0])
+        ones = self._ones(probe)
         grad, grad0, dpsi = torch.empty_like(psi), torch.zeros_like(psi), torch.zeros_like(psi)
         if recover_prb:
             gprb, gprb0, dprb = (torch.zeros_like(probe[:, 0]) for _ in range(3))
@@ -860,21 +895,12 @@ class CGPtychoSolver(PtychoHIP):
                 line_search(1, 0, S)
                 nat.check(nat.cg_prb_finish(h, sp, _ptr(probe), _ptr(dprb), S))
 
-        if self.verbose:
-            print("# congujate gradient parameters\n"
-                  "iteration, step size object, step size probe, function min")
+        self._log_header()
         try:
             for i in range(piter):
                 iteration(int(i == 0), int(i > 0))
                 if i % self.log_every == 0:
-                    snap = st[:nat.ST_LS_FAILED + 1].clone()
-                    if dist_on:
-                        self._allreduce(snap[nat.ST_COST:nat.ST_COST + 1])
-                    snap = snap.cpu()
-                    self.history.append((i, float(snap[nat.ST_GAMMA_PSI]), float(snap[nat.ST_GAMMA_PRB]),
-                                         float(snap[nat.ST_COST].to(torch.float32))))
-                    if self.verbose:
-                        print("%4d, %.3e, %.3e, %.7e" % self.history[-1])
+                    self._log_state(i, st)
         finally:
             # the native loop moved scan behind torch's back: forget what the operator calls knew about it
             self._scan_key = None
@@ -882,11 +908,7 @@ class CGPtychoSolver(PtychoHIP):
             nat.check(nat.set_option(self._h, b"trust_order", 0))
             nat.check(nat.set_option(self._h, b"ls_fused_decide", 0))
             nat.check(nat.set_option(self._h, b"defer_finish", 0))
-        failed = int(st[nat.ST_LS_FAILED].item())
-        if failed:
-            st[nat.ST_LS_FAILED] = 0.0
-            for _ in range(failed):
-                warnings.warn("Line search failed for conjugate gradient.")
+        self._replay_ls_failures(st)
         return {"psi": psi, "probe": probe}
 
     def _run_fused(self, data, psi, scan, probe, piter, recover_prb):
@@ -907,9 +929,7 @@ class CGPtychoSolver(PtychoHIP):
         dpsi = gradpsi0 = None
         dprb = gradprb0 = None
         gammaprb = 0
-        if self.verbose:
-            print("# congujate gradient parameters\n"
-                  "iteration, step size object, step size probe, function min")
+        self._log_header()
         for i in range(piter):
             # 1) object step ----------------------------------------------------------
             self._cg_fwd_cols(0, psi, scan, probe[:, 0])
@@ -954,9 +974,7 @@ class CGPtychoSolver(PtychoHIP):
             if i % self.log_every == 0:
                 c = cost.clone()
                 self._allreduce(c)
-                self.history.append((i, float(gammapsi), float(gammaprb), float(c.to(torch.float32))))
-                if self.verbose:
-                    print("%4d, %.3e, %.3e, %.7e" % self.history[-1])
+                self._log(i, float(gammapsi), float(gammaprb), float(c.to(torch.float32)))
         return {"psi": psi, "probe": probe}
 
     # -- fused multi-mode gaussian loop ----------------------------------------------------
@@ -988,11 +1006,7 @@ class CGPtychoSolver(PtychoHIP):
         nat.check(nat.set_option(self._h, b"compact_modes", M))
         self._scan_key = None                   # the position order becomes chunk-major: sort again
         nscan_total = self._nscan_total()
-        st = self.__dict__.get("_cg_state")
-        if st is None or st.device != dev:
-            st = self._cg_state = torch.zeros(nat.ST_WORDS, dtype=torch.float64, device=dev)
-            st[nat.ST_HINT:nat.ST_HINT + 2] = 14.0
-        st[nat.ST_GAMMA_PSI:nat.ST_GAMMA_PRB + 1] = 0.0
+        st = self._state(dev)
         sp = _ptr(st)
         sums = st[nat.ST_A:nat.ST_A + 2]                    # a, b (views of the state vector)
         cost = st[nat.ST_COST:nat.ST_COST + 1]
@@ -1049,9 +1063,7 @@ class CGPtychoSolver(PtychoHIP):
         dpsi = gradpsi0 = None
         dprb = gradprb0 = gradprb = None
         powers = None
-        if self.verbose:
-            print("# congujate gradient parameters\n"
-                  "iteration, step size object, step size probe, function min")
+        self._log_header()
         try:
             for i in range(piter):
                 # 1) object step ------------------------------------------------------------
@@ -1103,13 +1115,7 @@ class CGPtychoSolver(PtychoHIP):
                         nat.check(nat.cg_adj_cols(self._h, B, _ptr(psi), _ptr(scan), _ptr(g), 1, _stream()))
                         self._allreduce(g)
                         gradprb[:, m] = g / torch.max(torch.abs(psi)) ** 2 / nscan_total * prb_scale
-                        if i == 0:
-                            dprb[:, m] = -gradprb[:, m]
-                        else:
-                            dprb[:, m] = -gradprb[:, m] + (
-                                torch.linalg.norm(gradprb[:, m]) ** 2
-                                / (torch.sum(torch.conj(dprb[:, m]) * (gradprb[:, m] - gradprb0[:, m])))
-                                * dprb[:, m])
+                        dprb[:, m] = _dy_direction(i, gradprb[:, m], gradprb0[:, m], dprb[:, m])
                         gradprb0[:, m] = gradprb[:, m]
                         self._cg_fwd_cols(B, psi, scan, mode(dprb, m))
                         probe_line_search(m)                                        # -> state[GAMMA_PRB]
@@ -1118,22 +1124,11 @@ class CGPtychoSolver(PtychoHIP):
                         powers = orthogonalize_modes(probe, dprb, gradprb0)
 
                 if i % self.log_every == 0:
-                    snap = st[:nat.ST_LS_FAILED + 1].clone()
-                    if dist_on:
-                        self._allreduce(snap[nat.ST_COST:nat.ST_COST + 1])
-                    snap = snap.cpu()
-                    self.history.append((i, float(snap[nat.ST_GAMMA_PSI]), float(snap[nat.ST_GAMMA_PRB]),
-                                         float(snap[nat.ST_COST].to(torch.float32))))
-                    if self.verbose:
-                        print("%4d, %.3e, %.3e, %.7e" % self.history[-1])
+                    self._log_state(i, st)
         finally:
             nat.check(nat.set_option(self._h, b"compact_modes", 0))
             self._scan_key = None
-        failed = int(st[nat.ST_LS_FAILED].item())
-        if failed:
-            st[nat.ST_LS_FAILED] = 0.0
-            for _ in range(failed):
-                warnings.warn("Line search failed for conjugate gradient.")
+        self._replay_ls_failures(st)
         out = {"psi": psi, "probe": probe}
         if powers is not None:
             out["mode_powers"] = powers
@@ -1277,17 +1272,21 @@ class CGPtychoSolver(PtychoHIP):
         else:
             minf_ls = minf
 
+        def residual(f, inten):
+            if model == "gaussian":
+                return keep(f - torch.sqrt(data) * f / (torch.sqrt(inten) + 1e-32))
+            return keep(f - data * f / (inten + 1e-32))
+
         def intensity(obj):
             acc = torch.zeros_like(data)
             for k in range(nmodes):
                 acc += torch.abs(self.fwd(obj, scan, probe[:, k])) ** 2
             return keep(acc)
 
+        prb_scale = nmodes if model == "gaussian" else 1    # ptycho.py:431 (gaussian) / :441 (poisson)
         dprb = dpsi = gradprb0 = gradpsi0 = 0
         powers = None
-        if self.verbose:
-            print("# congujate gradient parameters\n"
-                  "iteration, step size object, step size probe, function min")
+        self._log_header()
         gammaprb = 0
         for i in range(piter):
             # 1) object retrieval subproblem with fixed probes -- :325-405
@@ -1299,31 +1298,12 @@ class CGPtychoSolver(PtychoHIP):
             absfpsi *= (a / b) ** 2
             gradpsi = torch.zeros((self.ptheta, self.nz, self.n), dtype=torch.complex64,
                                   device=data.device)
-            if model == "gaussian":
-                for k in range(nmodes):
+            for k in range(nmodes):
+                if model != "poisson":          # reference bug kept: its poisson branch reads fpsi and never assigns it
                     fpsi = self.fwd(psi, scan, probe[:, k]) * (b / a)
-                    gradpsi += self.adj(
-                        keep(fpsi - torch.sqrt(data) * fpsi / (torch.sqrt(absfpsi) + 1e-32)),
-                        scan, probe[:, k]) / (torch.max(torch.abs(probe[:, k])) ** 2)
-            elif model == "poisson":
-                for k in range(nmodes):
-                    gradpsi += self.adj(
-                        keep(fpsi - data * fpsi / (absfpsi + 1e-32)),    # noqa: F821 (reference bug kept)
-                        scan, probe[:, k]) / (torch.max(torch.abs(probe[:, k])) ** 2)
-            elif model == "poisson_ml":                   # the poisson branch with fpsi defined as above
-                for k in range(nmodes):
-                    fpsi = self.fwd(psi, scan, probe[:, k]) * (b / a)
-                    gradpsi += self.adj(
-                        keep(fpsi - data * fpsi / (absfpsi + 1e-32)),
-                        scan, probe[:, k]) / (torch.max(torch.abs(probe[:, k])) ** 2)
+                gradpsi += self.adj(residual(fpsi, absfpsi), scan, probe[:, k]) / (torch.max(torch.abs(probe[:, k])) ** 2)
             self._allreduce(gradpsi)
-            # Dai-Yuan direction
-            if i == 0:
-                dpsi = -gradpsi
-            else:
-                dpsi = -gradpsi + (
-                    torch.linalg.norm(gradpsi) ** 2
-                    / (torch.sum(torch.conj(dpsi) * (gradpsi - gradpsi0))) * dpsi)
+            dpsi = _dy_direction(i, gradpsi, gradpsi0, dpsi)
             gradpsi0 = gradpsi
             p1, p2, p3 = torch.zeros_like(data), torch.zeros_like(data), torch.zeros_like(data)
             for k in range(nmodes):
@@ -1352,23 +1332,10 @@ class CGPtychoSolver(PtychoHIP):
                 for m in range(nmodes):
                     fprb = self.fwd(psi, scan, probe[:, m])
                     absfprb = intensity(psi)
-                    if model == "gaussian":
-                        g = self.adj_probe(
-                            keep(fprb - torch.sqrt(data) * fprb / (torch.sqrt(absfprb) + 1e-32)),
-                            scan, psi)
-                        self._allreduce(g)
-                        gradprb[:, m] = g / torch.max(torch.abs(psi)) ** 2 / nscan_total * nmodes
-                    elif model in ("poisson", "poisson_ml"):
-                        g = self.adj_probe(keep(fprb - data * fprb / (absfprb + 1e-32)), scan, psi)
-                        self._allreduce(g)
-                        gradprb[:, m] = g / torch.max(torch.abs(psi)) ** 2 / nscan_total
-                    if i == 0:
-                        dprb[:, m] = -gradprb[:, m]
-                    else:
-                        dprb[:, m] = -gradprb[:, m] + (
-                            torch.linalg.norm(gradprb[:, m]) ** 2
-                            / (torch.sum(torch.conj(dprb[:, m]) * (gradprb[:, m] - gradprb0[:, m])))
-                            * dprb[:, m])
+                    g = self.adj_probe(residual(fprb, absfprb), scan, psi)
+                    self._allreduce(g)
+                    gradprb[:, m] = g / torch.max(torch.abs(psi)) ** 2 / nscan_total * prb_scale
+                    dprb[:, m] = _dy_direction(i, gradprb[:, m], gradprb0[:, m], dprb[:, m])
                     gradprb0[:, m] = gradprb[:, m]
                     p1 = intensity(psi)
                     tmp1 = self.fwd(psi, scan, probe[:, m])
@@ -1383,9 +1350,7 @@ class CGPtychoSolver(PtychoHIP):
             # check convergence -- :475-482 (cost of the start-of-iteration intensity)
             if i % self.log_every == 0:
                 cost = float(minf(absfpsi))
-                self.history.append((i, float(gammapsi), float(gammaprb), cost))
-                if self.verbose:
-                    print("%4d, %.3e, %.3e, %.7e" % self.history[-1])
+                self._log(i, float(gammapsi), float(gammaprb), cost)
         out = {"psi": psi, "probe": probe}
         if powers is not None:
             out["mode_powers"] = powers

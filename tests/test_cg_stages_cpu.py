@@ -1,5 +1,5 @@
 """Pin the stage reference of ``tests/cg_stages.py`` against the CG oracles: composed into the first object iteration,
-the stage functions must give what ``OracleSolver.run``, ``MaskedOracleSolver.run`` and ``PoissonOracleSolver.run``
+the stage functions must give what ``OracleSolver.run`` and, with a mask or the poisson_ml model, ``ReferenceSolver.run``
 compute -- the probe rescale a / b, the projected residual of every mode, the object gradient, the logged cost and the
 accepted step -- with and without a mask, for one and three probe modes.  The oracles' intermediates are read by
 wrapping the solver instance's ``adj`` (their logic is not touched).  No GPU."""
@@ -11,8 +11,7 @@ from oracle.cg_oracle import OracleSolver
 from libtike.hipfft import synthetic as syn
 
 import cg_stages as cs
-from masked_cg import MaskedOracleSolver, random_mask
-from poisson_cg import PoissonOracleSolver
+from cg_reference import ReferenceSolver, random_mask
 
 
 def setup(ndet, nmodes, masked, seed=3):
@@ -39,7 +38,7 @@ def first_iteration(ndet, nmodes, masked, model):
     """The oracle's first object iteration (probe rescale, residuals, gradient, cost, step) and the same composed from
     the stage functions."""
     p, probes, psi0, data, mask = setup(ndet, nmodes, masked)
-    cls = PoissonOracleSolver if model == "poisson_ml" else (MaskedOracleSolver if masked else OracleSolver)
+    cls = ReferenceSolver if model == "poisson_ml" or masked else OracleSolver
     slv = cls(p["nscan"], ndet, ndet, 1, p["nz"], p["n"], precision="double")
     seen = []
     orig_adj = slv.adj

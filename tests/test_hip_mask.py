@@ -1,5 +1,5 @@
 """Measured-pixel mask of the CG reconstruction on the GPU: ``CGPtychoSolver.run(..., mask=)`` on every loop (native,
-fused, multi-mode, statement-by-statement torch), against the masked NumPy reference of tests/masked_cg.py."""
+fused, multi-mode, statement-by-statement torch), against the NumPy reference of tests/cg_reference.py."""
 import ctypes
 import os
 import sys
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from masked_cg import MaskedOracleSolver, detector_mask, random_mask  # noqa: E402
+from cg_reference import ReferenceSolver, detector_mask, random_mask  # noqa: E402
 import recon_metrics as rm  # noqa: E402
 from libtike.hipfft import synthetic as syn  # noqa: E402
 
@@ -31,7 +31,7 @@ def problem(ndet, nmodes=1, seed=7, ny=6, step=6):
     probe = syn.hermite_modes(ndet, nmodes) if nmodes > 1 else p["probe"][:, None].copy()
     rng = np.random.default_rng(seed + 100)
     probe = (probe * np.exp(2j * np.pi * rng.random(probe.shape[-2:]))).astype(np.complex64)
-    ora = MaskedOracleSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
+    ora = ReferenceSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
     data = np.zeros((1, p["nscan"], ndet, ndet), np.float32)
     for k in range(nmodes):
         data += np.abs(ora.fwd(p["psi"], p["scan"], probe[:, k])) ** 2
@@ -114,7 +114,7 @@ def test_masked_cg_tracks_the_masked_reference(pt, ndet, nmodes, recover):
     mask = detector_mask(ndet, seed=ndet)
     start = probe.swapaxes(2, 3).copy() if recover else probe.copy()
     piter = 5
-    ora = MaskedOracleSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
+    ora = ReferenceSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         want = ora.run(data.copy(), np.ones_like(p["psi"]), p["scan"].copy(), start.copy(), piter=piter,

@@ -1,6 +1,6 @@
 """Orthogonal probe modes on the GPU: ``libtike.hipfft.orthogonalize_modes`` (C ABI ``ptycho_orthogonalize_modes``)
 against the float64 NumPy reference of tests/ortho_modes.py, and ``CGPtychoSolver.run(..., ortho_prb=True)`` on the fused
-multi-mode loop and the torch loop against the reference loop of tests/ortho_cg.py."""
+multi-mode loop and the torch loop against the reference loop of tests/cg_reference.py."""
 import os
 import sys
 import warnings
@@ -11,8 +11,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ortho_modes as om  # noqa: E402
 from cg_cases import phase_screen  # noqa: E402
-from masked_cg import detector_mask  # noqa: E402
-from ortho_cg import OrthoOracleSolver  # noqa: E402
+from cg_reference import ReferenceSolver, detector_mask  # noqa: E402
 from test_hip_poisson import horizon  # noqa: E402  (its UNRESOLVED_STEP rule)
 import recon_metrics as rm  # noqa: E402
 from libtike.hipfft import synthetic as syn  # noqa: E402
@@ -101,7 +100,7 @@ def problem(ndet, nmodes, seed=7, ny=6, step=6, dose=None):
     """Non-orthogonal smooth modes under a phase screen; the noiseless intensities (dose=None) or Poisson-sampled data."""
     p = syn.make_problem(ny, ny, step, ndet, ndet, seed=seed)
     probe = phase_screen(om.mode_stack(ndet, nmodes, seed=seed), seed + 100)
-    ora = OrthoOracleSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
+    ora = ReferenceSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
     inten = np.zeros((1, p["nscan"], ndet, ndet), np.float32)
     for k in range(nmodes):
         inten += np.abs(ora.fwd(p["psi"], p["scan"], probe[:, k])) ** 2
@@ -133,7 +132,7 @@ def gpu_run(slv, p, probe, data, piter, **kw):
 
 def reference(p, start, data, piter, precision, **kw):
     ndet = data.shape[-1]
-    ora = OrthoOracleSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"], precision=precision)
+    ora = ReferenceSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"], precision=precision)
     scan = p["scan"].copy()
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")

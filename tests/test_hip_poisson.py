@@ -1,6 +1,6 @@
 """Poisson maximum-likelihood model of the CG reconstruction on the GPU: ``CGPtychoSolver.run(..., model="poisson_ml")``
 on every loop (native, host-driven fused, multi-mode, statement-by-statement torch), against the float64 NumPy reference
-of tests/poisson_cg.py, with and without the detector mask."""
+of tests/cg_reference.py, with and without the detector mask."""
 import os
 import sys
 import warnings
@@ -10,8 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from cg_cases import phase_screen  # noqa: E402
-from masked_cg import detector_mask  # noqa: E402
-from poisson_cg import PoissonOracleSolver  # noqa: E402
+from cg_reference import ReferenceSolver, detector_mask  # noqa: E402
 import recon_metrics as rm  # noqa: E402
 from libtike.hipfft import synthetic as syn  # noqa: E402
 
@@ -28,7 +27,7 @@ def pt():
 
 
 def intensity(p, probe):
-    ora = PoissonOracleSolver(p["nscan"], probe.shape[-1], probe.shape[-1], 1, p["nz"], p["n"])
+    ora = ReferenceSolver(p["nscan"], probe.shape[-1], probe.shape[-1], 1, p["nz"], p["n"])
     inten = np.zeros((1, p["nscan"], probe.shape[-1], probe.shape[-1]), np.float32)
     for k in range(probe.shape[1]):
         inten += np.abs(ora.fwd(p["psi"], p["scan"], probe[:, k])) ** 2
@@ -75,7 +74,7 @@ def gpu_run(slv, p, probe, data, piter=4, recover=True, psi=None, model="poisson
 
 def reference(p, start, data, piter, recover, precision, psi=None, mask=None):
     ndet = data.shape[-1]
-    ora = PoissonOracleSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"], precision=precision)
+    ora = ReferenceSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"], precision=precision)
     scan = p["scan"].copy()
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")

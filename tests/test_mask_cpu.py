@@ -1,4 +1,4 @@
-"""Measured-pixel mask of the CG reconstruction, host side: the masked NumPy reference (tests/masked_cg.py), the C ABI's
+"""Measured-pixel mask of the CG reconstruction, host side: the NumPy reference with a mask (tests/cg_reference.py), the C ABI's
 argument checks, the solver signature and the I/O adapters.  No GPU needed."""
 import inspect
 import os
@@ -13,7 +13,7 @@ from libtike.hipfft import synthetic as syn
 from oracle import cg_oracle as cg
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from masked_cg import MaskedOracleSolver, detector_mask, random_mask  # noqa: E402
+from cg_reference import ReferenceSolver, detector_mask, random_mask  # noqa: E402
 
 
 def problem(nmodes, ndet=16, seed=3):
@@ -44,7 +44,7 @@ def run(cls, p, probe, data, mask=None, piter=5, recover=True):
 def test_all_ones_mask_is_the_oracle_bitwise(nmodes):
     p, probe, data = problem(nmodes)
     want, wscan, whist = run(cg.OracleSolver, p, probe, data)
-    got, gscan, ghist = run(MaskedOracleSolver, p, probe, data, mask=np.ones(data.shape[-2:], np.float32))
+    got, gscan, ghist = run(ReferenceSolver, p, probe, data, mask=np.ones(data.shape[-2:], np.float32))
     assert np.array_equal(got["psi"], want["psi"])
     assert np.array_equal(got["probe"], want["probe"])
     assert np.array_equal(gscan, wscan)
@@ -58,8 +58,8 @@ def test_masked_reference_ignores_unmeasured_data(garbage):
     assert 0 < (mask == 0).sum() < mask.size
     zero = np.where(mask != 0, data, 0).astype(np.float32)
     bad = np.where(mask != 0, data, garbage).astype(np.float32)
-    want, wscan, whist = run(MaskedOracleSolver, p, probe, zero, mask=mask, piter=4)
-    got, gscan, ghist = run(MaskedOracleSolver, p, probe, bad, mask=mask, piter=4)
+    want, wscan, whist = run(ReferenceSolver, p, probe, zero, mask=mask, piter=4)
+    got, gscan, ghist = run(ReferenceSolver, p, probe, bad, mask=mask, piter=4)
     assert np.isfinite(got["psi"]).all()
     assert np.array_equal(got["psi"], want["psi"]) and np.array_equal(got["probe"], want["probe"])
     assert np.array_equal(gscan, wscan) and ghist == whist
@@ -69,8 +69,8 @@ def test_masked_reference_differs_from_unmasked():
     """The mask changes the sums: a random 30 % mask on consistent data moves the cost and the trajectory."""
     p, probe, data = problem(1)
     mask = random_mask(data.shape[-1])
-    a, _, ha = run(MaskedOracleSolver, p, probe, data, mask=mask, piter=3)
-    b, _, hb = run(MaskedOracleSolver, p, probe, data, piter=3)
+    a, _, ha = run(ReferenceSolver, p, probe, data, mask=mask, piter=3)
+    b, _, hb = run(ReferenceSolver, p, probe, data, piter=3)
     assert ha[0][3] < hb[0][3]
     assert not np.array_equal(a["psi"], b["psi"])
 
@@ -78,9 +78,9 @@ def test_masked_reference_differs_from_unmasked():
 def test_masked_reference_rejects_bad_masks():
     p, probe, data = problem(1)
     with pytest.raises(ValueError):
-        run(MaskedOracleSolver, p, probe, data, mask=np.ones((8, 8)), piter=1)
+        run(ReferenceSolver, p, probe, data, mask=np.ones((8, 8)), piter=1)
     with pytest.raises(ValueError):
-        run(MaskedOracleSolver, p, probe, data, mask=np.zeros(data.shape[-2:]), piter=1)
+        run(ReferenceSolver, p, probe, data, mask=np.zeros(data.shape[-2:]), piter=1)
 
 
 def test_test_masks_layout():

@@ -1,4 +1,4 @@
-"""Orthogonal probe modes, host side: the NumPy reference of tests/ortho_modes.py and tests/ortho_cg.py held to its
+"""Orthogonal probe modes, host side: the NumPy reference of tests/ortho_modes.py and tests/cg_reference.py held to its
 defining properties, the Jacobi solve of csrc/k_modes.hpp built with the host compiler against numpy.linalg.eigh, and
 the C ABI's argument checks.  No GPU needed."""
 import ctypes
@@ -11,12 +11,12 @@ import numpy as np
 import pytest
 
 from libtike.hipfft import synthetic as syn
+from oracle import cg_oracle as cg
 from oracle import ptycho_oracle as op
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ortho_modes as om  # noqa: E402
-from ortho_cg import OrthoOracleSolver  # noqa: E402
-from masked_cg import MaskedOracleSolver  # noqa: E402
+from cg_reference import ReferenceSolver  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "libtike-cufft_amd", "csrc")
@@ -162,7 +162,7 @@ def test_host_jacobi_diagonal_input_is_a_permutation(host_jacobi):
 def cg_problem(nmodes, ndet=16, seed=3):
     p = syn.make_problem(4, 4, 4, ndet, ndet, seed=seed)
     probe = syn.hermite_modes(ndet, nmodes)
-    ora = OrthoOracleSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
+    ora = ReferenceSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
     data = np.zeros((1, p["nscan"], ndet, ndet), np.float32)
     for k in range(nmodes):
         data += np.abs(ora.fwd(p["psi"], p["scan"], probe[:, k])) ** 2
@@ -177,15 +177,15 @@ def cg_run(cls, p, start, data, **kw):
     scan = p["scan"].copy()
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        res = slv.run(data.copy(), np.ones_like(p["psi"]), scan, start.copy(), piter=3, recover_prb=True, **kw)
+        res = slv.run(data.copy(), np.ones_like(p["psi"]), scan, start.copy(), piter=3, **{"recover_prb": True, **kw})
     return res, slv
 
 
 @pytest.mark.parametrize("model", ["gaussian", "poisson_ml"])
 def test_cg_reference_returns_orthogonal_modes(model):
     p, start, data = cg_problem(3)
-    res, slv = cg_run(OrthoOracleSolver, p, start, data, ortho_prb=True, model=model)
-    plain, pslv = cg_run(OrthoOracleSolver, p, start, data, ortho_prb=False, model=model)
+    res, slv = cg_run(ReferenceSolver, p, start, data, ortho_prb=True, model=model)
+    plain, pslv = cg_run(ReferenceSolver, p, start, data, ortho_prb=False, model=model)
     g = om.gram(res["probe"])[0]
     d = np.diag(g).real
     assert np.abs(g - np.diag(np.diag(g))).max() <= 1e-5 * d.max()
@@ -195,11 +195,25 @@ def test_cg_reference_returns_orthogonal_modes(model):
     assert not np.array_equal(res["probe"], plain["probe"])
 
 
-def test_cg_reference_without_ortho_is_the_masked_loop():
-    p, start, data = cg_problem(2)
-    a, sa = cg_run(OrthoOracleSolver, p, start, data, ortho_prb=False)
-    b, sb = cg_run(MaskedOracleSolver, p, start, data)
+def test_cg_reference_without_ortho_is_the_oracle():
+    """ortho_prb=False is the oracle's loop bit for bit, and so is ortho_prb=True where it does not act (one mode, or no
+    probe recovery)."""
+    for nmodes, recover, ortho in [(2, True, False), (1, True, False), (3, True, False), (1, False, False),
+                                   (3, False, False), (1, True, True), (3, False, True)]:
+        p, start, data = cg_problem(nmodes)
+        a, sa = cg_run(ReferenceSolver, p, start, data, ortho_prb=ortho, recover_prb=recover)
+        b, sb = cg_run(cg.OracleSolver, p, start, data, recover_prb=recover)
+        assert np.array_equal(a["probe"], b["probe"]) and np.array_equal(a["psi"], b["psi"]), (nmodes, recover, ortho)
+        assert sa.history == sb.history, (nmodes, recover, ortho)
+
+
+@pytest.mark.parametrize("model", ["gaussian", "poisson_ml"])
+def test_cg_reference_all_ones_mask_is_no_mask_bitwise(model):
+    p, start, data = cg_problem(3)
+    a, sa = cg_run(ReferenceSolver, p, start, data, ortho_prb=True, model=model)
+    b, sb = cg_run(ReferenceSolver, p, start, data, ortho_prb=True, model=model, mask=np.ones(data.shape[-2:], np.float32))
     assert np.array_equal(a["probe"], b["probe"]) and np.array_equal(a["psi"], b["psi"]) and sa.history == sb.history
+    assert np.array_equal(sa.mode_powers, sb.mode_powers)
 
 
 # ---- C ABI ------------------------------------------------------------------------------------------------------------

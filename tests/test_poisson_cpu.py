@@ -1,4 +1,4 @@
-"""Poisson maximum-likelihood model of the CG reconstruction, host side: the NumPy reference of tests/poisson_cg.py held
+"""Poisson maximum-likelihood model of the CG reconstruction, host side: the NumPy reference of tests/cg_reference.py held
 to calculus, its mask rules, the models it keeps as they are, and the C ABI's model key.  No GPU needed."""
 import os
 import sys
@@ -12,8 +12,7 @@ from oracle import cg_oracle as cg
 from oracle import ptycho_oracle as op
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from masked_cg import detector_mask  # noqa: E402
-from poisson_cg import PoissonOracleSolver, poisson_cost, poisson_residual  # noqa: E402
+from cg_reference import ReferenceSolver, detector_mask, poisson_cost, poisson_residual  # noqa: E402
 
 
 def problem(nmodes, ndet=16, seed=3, dose=20.0):
@@ -32,7 +31,7 @@ def problem(nmodes, ndet=16, seed=3, dose=20.0):
 
 def run(p, probe, data, model="poisson_ml", mask=None, piter=5, recover=True, precision="single"):
     ndet = data.shape[-1]
-    slv = PoissonOracleSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"], precision=precision)
+    slv = ReferenceSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"], precision=precision)
     scan = p["scan"].copy()
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -130,16 +129,19 @@ def test_poisson_still_raises_and_poisson_ml_runs():
 
 
 def test_gaussian_reference_is_untouched():
-    """Every model but poisson_ml is MaskedOracleSolver.run (here: the oracle itself, bit for bit)."""
-    p, probe, data = problem(2)
-    got, gscan, ghist = run(p, probe, data, model="gaussian")
-    ora = cg.OracleSolver(p["nscan"], 16, 16, 1, p["nz"], p["n"])
-    scan = p["scan"].copy()
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        want = ora.run(data.copy(), np.ones_like(p["psi"]), scan, probe.copy().swapaxes(2, 3), piter=5, recover_prb=True)
-    assert np.array_equal(got["psi"], want["psi"]) and np.array_equal(got["probe"], want["probe"])
-    assert np.array_equal(gscan, scan) and ghist == ora.history
+    """With model="gaussian" the reference is the oracle itself, bit for bit: one and several modes, with and without
+    probe recovery."""
+    for nmodes, recover in [(2, True), (1, True), (3, True), (1, False), (3, False)]:
+        p, probe, data = problem(nmodes)
+        got, gscan, ghist = run(p, probe, data, model="gaussian", recover=recover)
+        ora = cg.OracleSolver(p["nscan"], 16, 16, 1, p["nz"], p["n"])
+        scan = p["scan"].copy()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            want = ora.run(data.copy(), np.ones_like(p["psi"]), scan, probe.copy().swapaxes(2, 3), piter=5,
+                           recover_prb=recover)
+        assert np.array_equal(got["psi"], want["psi"]) and np.array_equal(got["probe"], want["probe"]), (nmodes, recover)
+        assert np.array_equal(gscan, scan) and ghist == ora.history, (nmodes, recover)
 
 
 @pytest.fixture(scope="module")

@@ -1,6 +1,6 @@
 """CG iterations per second with and without a measured-pixel mask, alternating in one process, on bench.py's CG problem
 (4096 positions x 256^2, Gaussian probe, one mode, object = 1) and on configs[2] (4096 x 512^2, 4 Hermite modes).
-The mask is the "detector" mask of tests/masked_cg.py (beamstop, module gaps, 2 % dead pixels).
+The mask is the "detector" mask of tests/cg_reference.py (beamstop, module gaps, 2 % dead pixels).
 
     python tools/cg_mask_time.py [--only 256|cfg3] [--mask on|off] [--iters K] [--rounds R]
 
@@ -16,7 +16,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import libtike.hipfft as pt  # noqa: E402
 from libtike.hipfft import synthetic as syn  # noqa: E402
-from masked_cg import detector_mask  # noqa: E402
+from cg_reference import detector_mask  # noqa: E402
 
 
 def bench_problem(dev):
