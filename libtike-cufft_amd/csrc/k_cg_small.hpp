@@ -174,3 +174,8 @@ __global__ void k_cg_ls_decide(double* __restrict__ st, const int which, const i
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     ls_decide_dev(st, which, gamma_word, next_ngroups);
 }
+
+// start of a line search of the multi-mode loop, whose directions are not updated by k_cg_dy_update
+__global__ void k_cg_ls_begin(double* __restrict__ st, const int which) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) ls_prepare_dev(st, which);
+}

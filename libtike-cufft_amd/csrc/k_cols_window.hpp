@@ -75,7 +75,6 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
             const c32 v = win[slot];
             win[slot] = zero;
             const int X = X0 + col;
-            if ((PTY_AB & 8) && v.x != 123.456f) continue;   // A/B ablation (wrong results): price of the flush atomics
             if ((v.x != 0.0f || v.y != 0.0f) && Y < ge.nz && X >= 0 && X < ge.n) {
                 const size_t e = ((size_t)t_w * ge.nz + Y) * ge.n + X;
                 if (a.det_acc) {
@@ -113,9 +112,9 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
         return st;
     };
     auto tile_of = [&](const St& st, int k) {
-        // A/B ablation bit 16 (wrong results): 128-byte row pieces that straddle two 128-byte lines, as object-space bands
-        // (a workgroup owns 16 OBJECT columns: the tile columns it needs move with every position) would read them
-        return a.src + (size_t)(a.natural_tiles ? st.p : (k - a.k_begin)) * N * N + (((PTY_AB & 16) && k + 1 < a.k_end && st.p + 1 < ge.ptheta * ge.nscan) ? ((st.p & 7) + 1) : 0);
+        // (object-space bands -- a workgroup owns 16 OBJECT columns -- would read row pieces that straddle two 128-byte lines and
+        // reload the probe strip for every position: both priced and refuted, profiles/r04/adjwin_ablations.txt)
+        return a.src + (size_t)(a.natural_tiles ? st.p : (k - a.k_begin)) * N * N;
     };
 
     __syncthreads();
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
             continue;
         }
         const Pos q = st.q;
-        if (st.t != cur_t || (PTY_AB & 32)) {   // A/B bit 32: reloaded for every position (object-space bands would have to)
+        if (st.t != cur_t) {
             const c32* prb = a.aux + (size_t)st.t * ge.nprb * ge.nprb;
 #pragma unroll
             for (int m = 0; m < E; ++m) {
@@ -249,25 +248,15 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
                         int su = slot + u;
                         su = su >= H ? su - H : su;
                         wp[u] = win + su * WC + colw;
-                        if (PTY_AB & 64) { t0[u] = c32{w00, w01}; t1[u] = c32{w10, (float)u}; }   // A/B ablation: no tile reads
-                        else { t0[u] = tq[1]; t1[u] = tq[0]; }
+                        t0[u] = tq[1]; t1[u] = tq[0];
                     }
-                    if (PTY_AB & 128) {   // A/B ablation: no window read-modify-write (one store at the end of the trip keeps the sums alive)
-                        c32 accw = zero;
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            accw += t0[u] * w00 + t1[u] * w01 + up0 * w10 + up1 * w11;
-                            up0 = t0[u]; up1 = t1[u];
-                        }
-                        if (accw.x == 123.456f) *wp[0] = accw;
-                    } else {
+                    // (the floor without the tile reads / the window read-modify-write: profiles/r04/adjwin_ablations.txt)
 #pragma unroll
                     for (int u = 0; u < U; ++u) wv[u] = *wp[u];
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         *wp[u] = wv[u] + (t0[u] * w00 + t1[u] * w01 + up0 * w10 + up1 * w11);
                         up0 = t0[u]; up1 = t1[u];
-                    }
                     }
                     tp += U * CP;
                     slot += U;
