@@ -118,6 +118,43 @@ int ptycho_frc_prepare(void* out, const void* a, const void* b, size_t ptheta, s
                        size_t s, const float* window, void* stream);
 int ptycho_frc_rings(double* sums, const void* spec, size_t ptheta, size_t s, const double* shift, void* stream);
 
+/* Illumination map and gauge fixing (no handle; libtike.hipfft.gauge).  A ptychographic solution is defined up to one
+ * complex factor traded between object and probe and a linear phase ramp on the object paired with the opposite ramp on
+ * the probe; the poorly lit border means nothing.  Every launch runs on `stream`, nothing synchronises, no float atomics
+ * and fixed summation orders: the same inputs give the same bits.  ptheta in [1, 65535].
+ *   ptycho_illumination  out (float32 [ptheta][nz][n], written in full) <- the diagonal weight with which the object
+ *                        adjoint spreads |probe|^2: with A[t][iy][ix] = sum_m |probe[t][m][iy][ix]|^2 (probe complex64
+ *                        [ptheta][nmodes][nprb][nprb]) and position j of scan (float32 [ptheta][nscan][2], row first)
+ *                        split by modff into (sy, sx) + (fy, fx), out[t][sy+iy+a][sx+ix+b] += w_ab A[t][iy][ix] for a, b
+ *                        in {0, 1}, w_00 = (1-fx)(1-fy), w_01 = fx (1-fy), w_10 = (1-fx) fy, w_11 = fx fy.  A position
+ *                        with a negative integer part, a non-finite value or a value >= 1e9 is skipped; taps outside the
+ *                        object are dropped, the others kept.  One launch; per pixel the positions are added in index
+ *                        order, taps in the order above, in float32.
+ *   ptycho_gauge_fit     gauge (float64 [ptheta][6]) <- (gy, gx, phi0, s, yc, xc) per angle of psi (complex64
+ *                        [ptheta][nz][n]) against ref (same shape; NULL: u = psi) under weight (float32, >= 0, same
+ *                        shape; NULL: all ones), all sums in float64, u = psi conj(ref):
+ *                          gx = arg sum_{y, x<n-1} w[y][x] w[y][x+1] u[y][x+1] conj(u[y][x]), gy the same along y
+ *                          (arg 0 = 0; valid for |g| < pi rad / pixel);  W = sum w, yc = sum w y / W, xc = sum w x / W;
+ *                          phi0 = arg sum w u exp(-i (gy (y - yc) + gx (x - xc)));
+ *                          s = sqrt(sum w |psi|^2 / sum w |ref|^2) (without ref: / W), 1 if either sum is 0.
+ *                        W = 0 gives the identity (0, 0, 0, 1, 0, 0).  Pixels of weight 0 enter no sum, whatever they
+ *                        hold.  work: float64 scratch of ptheta * PTYCHO_GAUGE_WORK_PER_ANGLE words.  Four launches (two
+ *                        reduction passes, each followed by a one-workgroup-per-angle finish); the second pass reads
+ *                        the first one's result from gauge on the device.
+ *   ptycho_gauge_apply   in place on x (complex64 [ptheta][ny][nx]) with gauge (float64 [ptheta][6]):
+ *                        which = 0, object: x *= exp(-i (phi0 + gy (y - yc) + gx (x - xc))) / s;
+ *                        which = 1, probe companion: x *= s exp(+i (gy y + gx x)), local probe coordinates.
+ *                        Both applied (which = 1 to every probe mode) multiply each position's exit wave by a constant
+ *                        phase: the intensities stay (exactly at whole-pixel positions).  One launch.
+ * PTYCHO_ERR_ARG, before any HIP call, for a null out / scan / probe / gauge / psi / work / x, a zero size, nmodes < 1,
+ * which outside {0, 1}, ptheta > 65535 or a side too large for one launch (> 2^30; nz > 16 * 65535 for the illumination). */
+#define PTYCHO_GAUGE_WORK_PER_ANGLE 16384
+int ptycho_illumination(float* out, const void* scan, const void* probe, size_t ptheta, size_t nscan, int nmodes,
+                        size_t nprb, size_t nz, size_t n, void* stream);
+int ptycho_gauge_fit(double* gauge, const void* psi, const void* ref, const float* weight, size_t ptheta, size_t nz,
+                     size_t n, double* work, void* stream);
+int ptycho_gauge_apply(void* x, const double* gauge, size_t ptheta, size_t ny, size_t nx, int which, void* stream);
+
 /* ---- fused CG-stage entry points ("plus fused CG-stage entry points") ----
  * The elementwise stages of CGPtychoSolver.run (src/libtike/cufft/ptycho.py:325-393) are
  * fused into the row pass of the DFT so that farplanes are never materialised.  The

@@ -37,6 +37,7 @@
 #include "fft_core.hpp"
 #include "k_modes.hpp"
 #include "k_frc.hpp"
+#include "k_gauge.hpp"
 
 using namespace pty;
 
@@ -57,6 +58,7 @@ namespace {
 #include "host_handle.hpp"
 #include "host_ops.hpp"
 #include "host_cg.hpp"
+#include "host_gauge.hpp"
 
 extern "C" {
 
@@ -709,6 +711,40 @@ int ptycho_frc_rings(double* sums, const void* spec, size_t ptheta, size_t s, co
                        (int)s, shift);
     HIP_TRY(hipGetLastError());
     return PTYCHO_OK;
+}
+
+// ---- illumination map and gauge fixing (k_gauge.hpp, libtike.hipfft.gauge): no handle -----------------------------------
+int ptycho_illumination(float* out, const void* scan, const void* probe, size_t ptheta, size_t nscan, int nmodes,
+                        size_t nprb, size_t nz, size_t n, void* stream) {
+    if (!out || !scan || !probe) return fail(PTYCHO_ERR_ARG, "out, scan and probe must not be null");
+    if (ptheta == 0 || nscan == 0 || nprb == 0 || nz == 0 || n == 0) return fail(PTYCHO_ERR_ARG, "all sizes must be positive");
+    if (nmodes < 1) return fail(PTYCHO_ERR_ARG, "nmodes must be at least 1");
+    if (ptheta > kGaugeMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
+    if (nz > kGaugeMaxSide || n > kGaugeMaxSide || nprb > kGaugeMaxSide || nscan > 0x7fffffffull ||
+        (nz + kIllTileH - 1) / kIllTileH > 65535)
+        return fail(PTYCHO_ERR_ARG, "nz, n, nprb or nscan too large for one launch");
+    return do_illumination(out, (const float*)scan, (const c32*)probe, (int)ptheta, (int)nscan, nmodes, (int)nprb, (int)nz,
+                           (int)n, (hipStream_t)stream);
+}
+
+int ptycho_gauge_fit(double* gauge, const void* psi, const void* ref, const float* weight, size_t ptheta, size_t nz,
+                     size_t n, double* work, void* stream) {
+    if (!gauge || !psi || !work) return fail(PTYCHO_ERR_ARG, "gauge, psi and work must not be null");
+    if (ptheta == 0 || nz == 0 || n == 0) return fail(PTYCHO_ERR_ARG, "all sizes must be positive");
+    if (ptheta > kGaugeMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
+    if (nz > kGaugeMaxSide || n > kGaugeMaxSide) return fail(PTYCHO_ERR_ARG, "nz or n too large for one launch");
+    return do_gauge_fit(gauge, (const c32*)psi, (const c32*)ref, weight, (int)ptheta, (int)nz, (int)n, work,
+                        (hipStream_t)stream);
+}
+
+int ptycho_gauge_apply(void* x, const double* gauge, size_t ptheta, size_t ny, size_t nx, int which, void* stream) {
+    if (!x || !gauge) return fail(PTYCHO_ERR_ARG, "x and gauge must not be null");
+    if (ptheta == 0 || ny == 0 || nx == 0) return fail(PTYCHO_ERR_ARG, "all sizes must be positive");
+    if (which != 0 && which != 1) return fail(PTYCHO_ERR_ARG, "which must be 0 (object) or 1 (probe)");
+    if (ptheta > kGaugeMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
+    if (ny > kGaugeMaxSide || nx > kGaugeMaxSide || ((nx + 255) / 256) * ny > 0x7fffffffull)
+        return fail(PTYCHO_ERR_ARG, "ny or nx too large for one launch");
+    return do_gauge_apply((c32*)x, gauge, (int)ptheta, (int)ny, (int)nx, which, (hipStream_t)stream);
 }
 
 }  // extern "C"

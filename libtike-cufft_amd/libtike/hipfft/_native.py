@@ -28,6 +28,7 @@ SYMBOLS = ("ptycho_create", "ptycho_free", "ptycho_destroy", "ptycho_get",
            "ptycho_cg_cross_dev", "ptycho_cg_obj_begin2", "ptycho_cg_obj_dir2",
            "ptycho_set_mask", "ptycho_orthogonalize_modes",
            "ptycho_frc_prepare", "ptycho_frc_rings",
+           "ptycho_illumination", "ptycho_gauge_fit", "ptycho_gauge_apply",
            "ptycho_last_error", "ptycho_version")
 
 if not os.path.exists(LIB_PATH):
@@ -94,6 +95,14 @@ ORTHO_MAX_MODES = 16
 frc_prepare = _sig("ptycho_frc_prepare", _i, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _vp)
 #: sums, spec, ptheta, s, shift, stream
 frc_rings = _sig("ptycho_frc_rings", _i, _vp, _vp, _sz, _sz, _vp, _vp)
+#: illumination map (no handle): out, scan, probe, ptheta, nscan, nmodes, nprb, nz, n, stream
+illumination = _sig("ptycho_illumination", _i, _vp, _vp, _vp, _sz, _sz, _i, _sz, _sz, _sz, _vp)
+#: gauge, psi, ref, weight, ptheta, nz, n, work, stream
+gauge_fit = _sig("ptycho_gauge_fit", _i, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp)
+#: x, gauge, ptheta, ny, nx, which, stream
+gauge_apply = _sig("ptycho_gauge_apply", _i, _vp, _vp, _sz, _sz, _sz, _i, _vp)
+#: float64 words of ``gauge_fit``'s scratch per angle (PTYCHO_GAUGE_WORK_PER_ANGLE)
+GAUGE_WORK_PER_ANGLE = 16384
 #: ``get`` key: 1 if a measured-pixel mask is set on the handle
 GET_MASK = 102
 #: ``get`` key: option "model" of the CG stages that read data (MODEL_GAUSSIAN, MODEL_POISSON_ML)
