@@ -103,6 +103,8 @@ gauge_fit = _sig("ptycho_gauge_fit", _i, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp,
 gauge_apply = _sig("ptycho_gauge_apply", _i, _vp, _vp, _sz, _sz, _sz, _i, _vp)
 #: float64 words of ``gauge_fit``'s scratch per angle (PTYCHO_GAUGE_WORK_PER_ANGLE)
 GAUGE_WORK_PER_ANGLE = 16384
+#: ``get`` keys: options "chunk" and "window" as set; ``GET_WORK_SLOT0 + s``: 1 if CG work slot ``s`` holds device memory
+GET_CHUNK, GET_WINDOW, GET_WORK_SLOT0 = 100, 101, 200
 #: ``get`` key: 1 if a measured-pixel mask is set on the handle
 GET_MASK = 102
 #: ``get`` key: option "model" of the CG stages that read data (MODEL_GAUSSIAN, MODEL_POISSON_ML)

@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .ptycho import PtychoHIP, register_translation_batch, _ptr, _stream
+from .operators import PtychoHIP, _ptr, _stream
+from .registration import register_translation_batch
 
 __all__ = ["frc"]
 

@@ -18,7 +18,7 @@ import numbers
 import torch
 
 from . import _native as nat
-from .ptycho import _ptr, _stream
+from .operators import _ptr, _stream
 
 __all__ = ["illumination", "fit_gauge", "apply_gauge", "fix_gauge"]
 

@@ -79,6 +79,36 @@ def test_zoom_window_kernel_is_low_rank():
     assert P._zoom_real_factors(256, 150, 1, "cpu") is None      # a window that is not low rank
 
 
+def test_ptycho_facade_reexports(nat):
+    """``libtike.hipfft.ptycho`` stays the import point: the public names, and every private name that tests, tools and
+    sibling modules import from it, are the objects of the modules that now define them."""
+    from libtike.hipfft import ptycho as P, operators, registration, modes, cg
+    assert P.__all__ == ["PtychoHIP", "PtychoCuFFT", "CGPtychoSolver",
+                         "register_translation_batch", "orthogonalize_modes", "TorchArrayModule"]
+    homes = {operators: ("PtychoHIP", "PtychoCuFFT", "TorchArrayModule", "_ptr", "_stream"),
+             registration: ("register_translation_batch", "_zoom_real_factors", "_zoom_shifts_native",
+                            "_finish_registration", "_upsampled_dft_batch"),
+             modes: ("orthogonalize_modes",), cg: ("CGPtychoSolver",)}
+    for module, names in homes.items():
+        for name in names:
+            assert getattr(P, name) is getattr(module, name), name
+
+
+def test_zoom_kernel_eligibility(nat):
+    """``_zoom_kernel_factors`` accepts what the four call sites accepted one by one: a multiple of 16 up to 1024 with a
+    low-rank window, and nothing else."""
+    from libtike.hipfft.registration import _ZOOM_CACHE, _zoom_kernel_factors, _zoom_real_factors
+    for ndet in (40, 2048, 1040):
+        assert _zoom_kernel_factors(ndet, 100, "cpu") is None
+    for ndet in (48, 256, 1024):
+        fac = _zoom_kernel_factors(ndet, 100, "cpu")
+        assert len(fac) == 4 and fac[3] == 150 and fac[:3] == _zoom_real_factors(ndet, 150, 100, "cpu")
+    assert _zoom_kernel_factors(256, 1, "cpu") is None              # a window that is not low rank
+    assert _zoom_kernel_factors(64, 1000, "cpu", widest=256) is None
+    assert ("real", 64, 1500, 1000, 16, "cpu") not in _ZOOM_CACHE    # rejected before any factorisation
+    assert _zoom_kernel_factors(64, 100, "cpu", widest=256) is not None
+
+
 def test_fft_core_on_host(tmp_path):
     """Stockham index math of csrc/fft_core.hpp for every plan (16..2048, both
     directions) emulated thread by thread on the host against a naive DFT."""
