@@ -159,12 +159,16 @@ __global__ void k_cg_dy_update(c32* __restrict__ d, c32* __restrict__ g0, const 
     }
 }
 
-// x <- x + gamma d with gamma = (float)*gamma_word; product and sum rounded separately, like the array expression
+// x <- x + gamma d with gamma = (float)*gamma_word; product and sum rounded separately, like the array expression.
+// (__fmul_rn / __fadd_rn are plain * and + in this toolchain and were contracted into one v_pk_fma_f32 under hipcc's default
+// -ffp-contract=fast; the pragma is what keeps the two roundings.)
 __global__ void k_cg_axpy(c32* __restrict__ x, const c32* __restrict__ d, const long long n, const double* __restrict__ gamma_word) {
+#pragma clang fp contract(off)
     const float gm = (float)*gamma_word;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const c32 xi = x[i], di = d[i];
-        x[i] = c32{__fadd_rn(xi.x, __fmul_rn(gm, di.x)), __fadd_rn(xi.y, __fmul_rn(gm, di.y))};
+        const float pr = gm * di.x, pi = gm * di.y;
+        x[i] = c32{xi.x + pr, xi.y + pi};
     }
 }
 

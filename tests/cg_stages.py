@@ -15,6 +15,11 @@ it.  The semantics restate the epilogue comments of ``k_rows_fused`` (``csrc/k_r
   the pixel's constant is subtracted, as the kernel does.
 * ``intensity_modes``, ``project_multi``, ``linesearch_modes``: the same over probe modes.
 * ``cross``: the image product ``u1 conj(u1 + gamma d1)`` and the first maximum of ``|IDFT2(product)|`` per position.
+* ``zoom``: the sub-pixel stage of the registration (``ptycho_cg_zoom``): the whole-pixel peak wrapped to
+  ``[-N/2, N/2]`` (an index above ``fix(N/2)`` loses ``N``; ``N/2`` itself stays positive), the ``ups x ups`` window
+  ``|conj(upsampled_dft(conj(product)))|`` around it and ``shift = peak + (argmax - fix(ups/2)) / upsample_factor``.
+* ``finish``: the tail of the object step for angle 0 (``ptycho_cg_obj_finish``): the registration of
+  ``fwd(psi, 1)[0]`` against ``fwd(psi, 1)[0] + gamma fwd(dpsi, 1)[0]`` and ``psi + gamma dpsi`` as float32 arithmetic.
 
 With a mask (nonzero = measured) data, the intensity and the line-search terms are selected to 0 at unmeasured pixels
 before any arithmetic (never multiplied: the data there may be NaN) and the residual is 0 there.
@@ -33,7 +38,7 @@ import numpy as np
 from oracle import ptycho_oracle as op
 
 __all__ = ["farplane", "stats", "project", "linesearch", "intensity_modes", "project_multi", "linesearch_modes",
-           "cross", "EPS"]
+           "cross", "zoom", "finish", "axpy32", "peak_product", "shifted_pair", "edge_indices", "wrap_index", "EPS"]
 
 EPS = 1e-32   # the regulariser of the residuals, the cost's logarithm and the line-search constant
 
@@ -225,3 +230,105 @@ def cross(U1, D1, gamma, precision="double"):
     top = a[np.arange(a.shape[0]), idx]
     second = np.partition(a, -2, axis=1)[:, -2]
     return ip, idx, top, second
+
+
+def zoom(ip, idx, upsample_factor, precision="double"):
+    """``ptycho_cg_zoom`` (``ptycho.py:209-235``): ``ip`` ``[nb, N, N]`` image products, ``idx`` the flat index
+    ``y N + x`` of the whole-pixel peak per position.  The product is taken in the given precision (complex64 for
+    "single"); everything after it is float64, as on the device.  Returns ``(window, peak, shifts, gap)``: the
+    ``[nb, ups, ups]`` magnitudes, the flat arg-max of each window (first maximum), the float64 ``[nb, 2]`` shifts and
+    per position the relative gap ``(top - second) / top`` between the largest and the second-largest window value
+    (``inf`` for an all-zero window, whose arg-max is index 0 by the first-maximum rule)."""
+    from oracle.cg_oracle import upsampled_dft_batch
+    ct, _ = _types(precision)
+    ip = np.asarray(ip).astype(ct).astype(np.complex128)
+    nb, nrow, ncol = ip.shape
+    idx = np.asarray(idx, dtype=np.int64)
+    shifts = np.stack((idx // ncol, idx % ncol), axis=1).astype(np.float64)
+    mid = [np.fix(nrow / 2), np.fix(ncol / 2)]
+    shifts[shifts[:, 0] > mid[0], 0] -= nrow
+    shifts[shifts[:, 1] > mid[1], 1] -= ncol
+    shifts = np.round(shifts * upsample_factor) / upsample_factor
+    ups = int(np.ceil(upsample_factor * 1.5))
+    dftshift = np.fix(ups / 2.0)
+    offset = dftshift - shifts * upsample_factor
+    window = np.zeros((nb, ups, ups))
+    live = np.nonzero(ip.reshape(nb, -1).any(axis=1))[0]      # an all-zero product has an all-zero window: no need to sum it
+    if live.size:
+        window[live] = np.abs(upsampled_dft_batch(ip[live].conj(), ups, upsample_factor, offset[live]).conj())
+    flat = window.reshape(nb, -1)
+    peak = flat.argmax(1)
+    top = flat[np.arange(nb), peak]
+    second = np.partition(flat, -2, axis=1)[:, -2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        gap = np.where(top > 0, (top - second) / top, np.inf)
+    maxima = np.stack((peak // ups, peak % ups), axis=1).astype(np.float64) - dftshift
+    return window, peak, shifts + maxima / upsample_factor, gap
+
+
+def axpy32(x, d, gamma):
+    """``x + float32(gamma) d`` as ``k_cg_axpy`` forms it: per real component a float32 product, rounded, then a float32
+    sum, rounded -- no fused multiply-add."""
+    x = np.asarray(x).astype(np.complex64)
+    d = np.asarray(d).astype(np.complex64)
+    g = np.float32(gamma)
+    out = np.empty_like(x)
+    out.real = x.real + (g * d.real).astype(np.float32)
+    out.imag = x.imag + (g * d.imag).astype(np.float32)
+    return out
+
+
+def finish(psi, dpsi, gamma, scan, ndet, upsample_factor=100, precision="double", nprb=None):
+    """``ptycho_cg_obj_finish`` for angle 0 (``ptycho.py:398-405``): ``tmp1 = fwd(psi, 1)[0]``,
+    ``tmp2 = tmp1 + float32(gamma) fwd(dpsi, 1)[0]`` with the all-ones probe of ``nprb`` pixels (default ``ndet``), the
+    registration of the two in Fourier space, and the object update.  Returns a dict: ``ip`` the image product
+    ``[nscan, ndet, ndet]``, ``idx`` / ``top`` / ``second`` the whole-pixel stage of ``cross``, ``window`` / ``peak`` /
+    ``shifts`` / ``gap`` of ``zoom`` and ``psi`` = ``axpy32(psi, dpsi, gamma)`` (all angles)."""
+    psi = np.asarray(psi)
+    nprb = ndet if nprb is None else nprb
+    ones = np.ones((psi.shape[0], nprb, nprb), np.complex64)
+    scan = np.asarray(scan)
+    U = farplane(psi[:1], scan[:1], ones[:1], ndet, precision)
+    D = farplane(np.asarray(dpsi)[:1], scan[:1], ones[:1], ndet, precision)
+    ip, idx, top, second = cross(U, D, gamma, precision)
+    window, peak, shifts, gap = zoom(ip[0], idx, upsample_factor, precision)
+    return dict(ip=ip[0], idx=idx, top=top, second=second, window=window, peak=peak, shifts=shifts, gap=gap,
+                psi=axpy32(psi, dpsi, gamma))
+
+
+# ---- inputs of the registration tests ------------------------------------------------------------------------------------
+def edge_indices(n):
+    """Whole-pixel peak indices at which the wrap to ``[-n/2, n/2]`` and the fftfreq ordering can go wrong."""
+    return [0, 1, n // 2 - 1, n // 2, n // 2 + 1, n - 1]
+
+
+def wrap_index(i, n):
+    """``ptycho.py:212-216``: an index above ``fix(n / 2)`` loses ``n``; ``n / 2`` itself stays positive."""
+    i = np.asarray(i, dtype=np.int64)
+    return np.where(i > n // 2, i - n, i)
+
+
+def peak_product(rng, ndet, true):
+    """Image products ``[nb, ndet, ndet]`` (complex64) whose correlation peaks at the shifts ``true`` ``[nb, 2]`` (pixels,
+    within ``[-ndet/2, ndet/2]``): a smooth positive base times the phase ramp of the shift, plus 5 % complex noise."""
+    true = np.asarray(true, dtype=np.float64)
+    nb = true.shape[0]
+    ky = np.fft.fftfreq(ndet)[None, :, None]
+    kx = np.fft.fftfreq(ndet)[None, None, :]
+    base = rng.standard_normal((nb, ndet, ndet)) ** 2 + 0.1
+    ip = base * np.exp(-2j * np.pi * (ky * true[:, 0, None, None] + kx * true[:, 1, None, None]))
+    return (ip + 0.05 * (rng.standard_normal(ip.shape) + 1j * rng.standard_normal(ip.shape))).astype(np.complex64)
+
+
+def shifted_pair(rng, shape, shift, gamma):
+    """``(psi, dpsi)``, complex64 ``shape`` = ``[ptheta, nz, n]``: ``psi`` is white (zero mean: the correlation of two
+    patches peaks at the shift only), ``psi2`` is ``psi`` moved by ``shift`` pixels with a Fourier phase ramp plus 5 %
+    noise, and ``dpsi = (psi2 - psi) / float32(gamma)``, so that ``psi + gamma dpsi`` is ``psi2`` up to rounding."""
+    def white():
+        return rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
+    psi = white().astype(np.complex64)
+    ky = np.fft.fftfreq(shape[-2])[:, None]
+    kx = np.fft.fftfreq(shape[-1])[None, :]
+    psi2 = np.fft.ifft2(np.fft.fft2(psi) * np.exp(-2j * np.pi * (ky * shift[0] + kx * shift[1])))
+    psi2 = (psi2 + 0.05 * white()).astype(np.complex64)
+    return psi, ((psi2 - psi) / np.float32(gamma)).astype(np.complex64)

@@ -159,3 +159,68 @@ def test_cross_finds_a_known_shift():
     want = ((-shift[0]) % ndet) * ndet + (-shift[1]) % ndet
     assert np.all(idx == want) and np.all(second < 0.5 * top)
     assert np.allclose(ip, (U * np.conj(V))[None])
+
+
+# ---- the registration tail: cs.zoom / cs.finish against the oracle's register_translation_batch ---------------------------
+def test_zoom_and_finish_reproduce_the_oracles_registration():
+    """``cs.finish`` (fwd with the ones probe, ``cs.cross``, ``cs.zoom``) gives the shifts of the oracle's
+    ``register_translation_batch(tmp1, tmp2, 100, "fourier")`` bit for bit, and the float32 object update."""
+    from oracle.cg_oracle import register_translation_batch
+    ndet, nprb = 16, 12
+    p = syn.make_problem(3, 3, 5, nprb, ndet, seed=4)
+    rng = np.random.default_rng(4)
+    gamma = 0.6
+    psi, dpsi = cs.shifted_pair(rng, p["psi"].shape, (1.37, -2.41), gamma)
+    scan = p["scan"].copy()
+    scan[0, 1] = [-1.5, 2.25]                                  # skipped: an all-zero tile
+    f = cs.finish(psi, dpsi, gamma, scan, ndet, 100, nprb=nprb)
+    ones = np.ones((1, nprb, nprb), np.complex64)
+    tmp1 = op.fwd(psi, scan, ones, ndet, "double")[0]
+    tmp2 = tmp1 + np.float32(gamma) * op.fwd(dpsi, scan, ones, ndet, "double")[0]
+    want = register_translation_batch(tmp1, tmp2, 100, "fourier")
+    assert np.array_equal(f["shifts"], want), (f["shifts"], want)
+    assert np.array_equal(f["ip"], tmp1 * np.conj(tmp2))
+    live = f["top"] > 0
+    assert live.sum() == len(live) - 1 and not live[1]
+    assert np.all(np.abs(f["shifts"][live] - [-1.37, 2.41]) < 0.1)      # the registration sees the move
+    assert np.all(f["gap"][live] > 1e-9)
+    # the object update: float32 product, then float32 sum (distinct from the float64 value, within float32 rounding)
+    g32 = np.float32(gamma)
+    exact = psi.astype(np.complex128) + np.float64(g32) * dpsi.astype(np.complex128)
+    assert f["psi"].dtype == np.complex64
+    assert np.abs(f["psi"] - exact).max() <= 2.0 ** -23 * np.abs(exact).max()
+    assert np.array_equal(f["psi"].real, psi.real + (g32 * dpsi.real).astype(np.float32))
+    # float32 farplanes give the same whole-pixel peaks
+    f32 = cs.finish(psi, dpsi, gamma, scan, ndet, 100, "single", nprb=nprb)
+    assert f32["ip"].dtype == np.complex64 and np.array_equal(f32["idx"][live], f["idx"][live])
+
+
+def test_an_all_zero_tile_moves_by_minus_three_quarters():
+    """Reference quirk: a skipped position has an all-zero tile, both arg-maxima are index 0 and the position moves by
+    ``(0 - fix(150 / 2)) / 100`` on each axis."""
+    from oracle.cg_oracle import register_translation_batch
+    z = np.zeros((2, 16, 16), np.complex128)
+    want = register_translation_batch(z, z, 100, "fourier")
+    assert np.array_equal(want, np.full((2, 2), -0.75))
+    window, peak, shifts, gap = cs.zoom(z, np.zeros(2, np.int64), 100)
+    assert np.array_equal(shifts, want) and np.all(peak == 0) and np.all(window == 0) and np.all(np.isinf(gap))
+
+
+@pytest.mark.parametrize("ndet", [16, 48])
+def test_zoom_wraps_the_edge_indices_as_the_oracle_does(ndet):
+    """Whole-pixel peaks at 0, 1, N/2 - 1, N/2, N/2 + 1 and N - 1 on either axis (all 36 pairs), sub-pixel parts of both
+    signs: the oracle finds the planted index, and ``cs.zoom`` from that index gives the oracle's shifts bit for bit."""
+    from oracle.cg_oracle import register_translation_batch
+    e = cs.edge_indices(ndet)
+    iy, ix = (a.ravel() for a in np.meshgrid(e, e, indexing="ij"))
+    rng = np.random.default_rng(ndet)
+    frac = rng.uniform(0.05, 0.45, (iy.size, 2)) * np.where(rng.random((iy.size, 2)) < 0.5, -1.0, 1.0)
+    assert (frac > 0).any(0).all() and (frac < 0).any(0).all()
+    whole = np.stack((cs.wrap_index(iy, ndet), cs.wrap_index(ix, ndet)), axis=1)
+    assert set(whole[:, 0]) == {0, 1, ndet // 2 - 1, ndet // 2, 1 - ndet // 2, -1}
+    ip = cs.peak_product(rng, ndet, whole + frac).astype(np.complex128)
+    want = register_translation_batch(ip, np.ones_like(ip), 100, "fourier")
+    window, peak, shifts, gap = cs.zoom(ip, iy * ndet + ix, 100)
+    assert np.array_equal(np.round(want), whole), "the oracle's whole-pixel stage finds the planted index"
+    assert np.array_equal(shifts, want)
+    assert np.abs(shifts - (whole + frac)).max() < 0.02 and np.all(gap > 1e-9)

@@ -11,6 +11,10 @@ Tolerances.  For every comparison the error of the float32 evaluation of the sam
 against float64 is measured on the same inputs; the device may be at most ``FACTOR`` times that error off, plus a floor
 no larger than the operator bounds: ``REL_MAX`` of the largest element for arrays, ``SUM_REL`` of the sum of the
 magnitudes of the terms for sums and costs (a cost near its minimum is bounded by its terms, not by its value).
+
+Section H covers the tail of the object and probe steps (``ptycho_cg_obj_finish`` by route, ``ptycho_cg_prb_finish``): there
+the object update must be bit-equal to its float32 restatement and a position's sub-pixel pick must lie within the float32
+image product's own distance from the float64 one of the float64 window's top (``check_positions``).
 """
 import ctypes
 
@@ -575,3 +579,191 @@ def test_deterministic_adjoints_are_scale_invariant(case):
     finally:
         c.slv.set_deterministic(False)
         torch.cuda.synchronize()
+
+
+# ---- H. the tail of the object and probe steps: position correction by route, scan += shifts, psi += gamma dpsi ---------
+REG_SIZES = (48, 64, 112, 192, 256, 512, 1024)
+REG_GAMMA = 0.6
+REG_SHIFT = (2.37, -3.41)
+UPS, UP = 150, 100                  # the window and the upsample factor of the loop (cg_device.py)
+
+
+def reg_case(c):
+    """Inputs of section H, made once per geometry: white psi, psi2 = psi moved by REG_SHIFT + 5 % noise,
+    dpsi = (psi2 - psi) / gamma; the case's scan with its skipped, -0.0, integer and overhanging positions."""
+    if not hasattr(c, "_reg"):
+        import torch
+        from libtike.hipfft.registration import _zoom_kernel_factors
+        P = c.P
+        rng = np.random.default_rng(11)
+        psi, dpsi = cs.shifted_pair(rng, P["psi"].shape, REG_SHIFT, REG_GAMMA)
+        fac = _zoom_kernel_factors(P["ndet"], UP, "cuda")
+        assert fac is not None and fac[3] == UPS
+        c._reg = dict(psi=psi, dpsi=dpsi, ones=torch.ones_like(c.prb), vt=fac[0], lz=fac[1], nc=fac[2],
+                      ref=reg_reference(c, psi, dpsi, REG_GAMMA))
+    return c._reg
+
+
+def reg_reference(c, psi, dpsi, gamma):
+    """cs.finish in float64, and the image product of the float32 evaluation: E32 = sum |ip32 - ip64| per position bounds
+    how far any window value of a float32 farplane can be off (every window-kernel entry has unit modulus)."""
+    P = c.P
+    f = cs.finish(psi, dpsi, gamma, P["scan"], P["ndet"], UP, nprb=P["nprb"])
+    ones = np.ones((1, P["nprb"], P["nprb"]), np.complex64)
+    ip32 = cs.cross(cs.farplane(psi[:1], P["scan"][:1], ones, P["ndet"], "single"),
+                    cs.farplane(dpsi[:1], P["scan"][:1], ones, P["ndet"], "single"), gamma, "single")[0][0]
+    f["e32"] = np.abs(ip32.astype(np.complex128) - f["ip"]).sum(axis=(1, 2))
+    return f
+
+
+def obj_finish(c, route, psi, dpsi, gamma, begin=None):
+    """ptycho_cg_obj_finish(route) on fresh copies of psi and the case's scan, the gamma word set by the caller; returns
+    (psi, scan) afterwards.  Route 2 runs ptycho_cg_reg_prepare first."""
+    nat, P_, S_ = nat_mod()
+    r = reg_case(c)
+    S = S_()
+    st = zeros64(nat.ST_WORDS)
+    st[nat.ST_GAMMA_PSI] = gamma
+    psi_d, dpsi_d, scan_d = c.D(psi), c.D(dpsi), c.scan.clone()
+    nat.check(nat.set_option(c.h, b"trust_order", 0))          # as the loop does: nothing is known about this scan
+    c.slv.profile(True)
+    if route == 2:
+        nat.check(nat.cg_reg_prepare(c.h, P_(st), P_(psi_d), P_(scan_d), P_(r["ones"]), S))
+    nat.check(nat.cg_obj_finish(c.h, P_(st), route, P_(psi_d), P_(dpsi_d), P_(scan_d), P_(r["ones"]), P_(r["vt"]), P_(r["lz"]),
+                                r["nc"], UPS, float(UP), S))
+    out = host(psi_d), host(scan_d)
+    prof = c.slv.profile_read()
+    c.slv.profile(False)
+    ran = {k: prof.get(k, (0.0, 0))[1] for k in ("k_rows_fused<CROSS>", "k_cols_argmax", "k_zoom_argmax")}
+    assert all(n == (1 if route else 0) for n in ran.values()), "correct_positions = %d launched %s" % (route, ran)
+    nat.check(nat.set_option(c.h, b"trust_order", 0))
+    return out
+
+
+def bits(x):
+    return np.ascontiguousarray(x).view(np.uint32)
+
+
+def check_positions(c, ref, scan_after, what):
+    """The rules of section H for angle 0.  The internal shifts are not visible: the 1/100-grid index is recovered from
+    scan_after - scan_before, such that float32(scan_before + float32(shift)) is scan_after bit for bit (the reference's
+    float32 in-place add) with the reference's whole-pixel part.  The farplanes are float32 on the device, so the pick may
+    sit on a neighbouring grid point: it is accepted only where the float64 window is within 2 FACTOR E32 of its top.
+    Returns (positions with a single acceptable grid point, live positions, largest E32 / top)."""
+    P = c.P
+    N = P["ndet"]
+    before = P["scan"][0]
+    live = ref["top"] > 0
+    assert live.sum() >= len(live) - 1, "only the skipped position has an all-zero tile"
+    assert np.all(ref["second"][live] < 0.9 * ref["top"][live]), "design: one clear peak per position"
+    whole = np.stack((cs.wrap_index(ref["idx"] // N, N), cs.wrap_index(ref["idx"] % N, N)), axis=1).astype(np.float64)
+    grid = (np.arange(UPS, dtype=np.float64) - float(UPS // 2)) / float(UP)
+    single = 0
+    worst = 0.0
+    for i in range(len(live)):
+        if not live[i]:
+            want = before[i] + np.float32(-0.75)
+            assert np.array_equal(bits(scan_after[0, i]), bits(want)), "%s: skipped position %d moved by %s" % (
+                what, i, scan_after[0, i] - before[i])
+            continue
+        pick = []
+        for ax in range(2):
+            cand = (before[i, ax] + (whole[i, ax] + grid).astype(np.float32)).astype(np.float32)
+            j = np.nonzero(bits(cand) == bits(scan_after[0, i, ax]))[0]
+            assert j.size == 1, "%s: position %d axis %d moved by %r: no shift of the reference's whole pixel %g on the 1/%d grid" % (
+                what, i, ax, scan_after[0, i, ax] - before[i, ax], whole[i, ax], UP)
+            pick.append(int(j[0]))
+        w = ref["window"][i]
+        top = w.max()
+        margin = 2 * FACTOR * ref["e32"][i]
+        worst = max(worst, ref["e32"][i] / top)
+        assert w[pick[0], pick[1]] >= top - margin, "%s: position %d picked (%d, %d), window %.17g, top %.17g at %s, margin %.3g" % (
+            what, i, pick[0], pick[1], w[pick[0], pick[1]], top, np.unravel_index(w.argmax(), w.shape), margin)
+        single += int((w >= top - margin).sum() == 1)
+    print("%s: %d of %d live positions with a single acceptable grid point, largest E32 / top %.3g" % (what, single, live.sum(), worst))
+    assert single >= live.sum() - 1, "design: the margin must leave one grid point (%s: %d of %d)" % (what, single, live.sum())
+    return single, int(live.sum()), worst
+
+
+def test_obj_finish_by_route(case):
+    """ptycho_cg_obj_finish with correct_positions 0, 1, 2 (after ptycho_cg_reg_prepare) and 3 (after obj_begin2 / obj_grad /
+    obj_dir2 with the ones probe) against cs.finish; the in-kernel scan[0] += shifts, angle 0 only; k_cg_axpy on all angles.
+    Routes 1 and 2 run the same kernels on the same operands, and the paired gather of route 3 multiplies the same patch by
+    the ones probe (exact) before the same column DFT, so all three must leave the same bits in scan."""
+    import torch
+    nat, P_, S_ = nat_mod()
+    c = case
+    P = c.P
+    if P["ndet"] not in REG_SIZES or P["nscan"] > 100:
+        pytest.skip("the registration tail at 48, 64, 112, 192, 256, 512, 1024")
+    r = reg_case(c)
+    psi, dpsi, ref = r["psi"], r["dpsi"], r["ref"]
+    # route 0: the object update alone
+    psi0, scan0 = obj_finish(c, 0, psi, dpsi, REG_GAMMA)
+    assert np.array_equal(bits(psi0), bits(ref["psi"])), "psi + gamma dpsi (float32 product, then float32 sum)"
+    assert np.array_equal(bits(scan0), bits(P["scan"])), "correct_positions = 0 moved the scan"
+    assert not np.array_equal(bits(psi0), bits(psi))
+    # route 1: own column passes
+    psi1, scan1 = obj_finish(c, 1, psi, dpsi, REG_GAMMA)
+    assert np.array_equal(bits(psi1), bits(ref["psi"]))
+    check_positions(c, ref, scan1, "route 1 %s" % gid(c.g))
+    assert np.array_equal(bits(scan1[1:]), bits(P["scan"][1:])), "only angle 0 is corrected"
+    assert not np.array_equal(bits(scan1[0]), bits(P["scan"][0]))
+    again = obj_finish(c, 1, psi, dpsi, REG_GAMMA)
+    assert np.array_equal(bits(again[0]), bits(psi1)) and np.array_equal(bits(again[1]), bits(scan1)), "route 1 twice"
+    # route 2: slot 2 prepared; the same kernels on the same operands
+    psi2, scan2 = obj_finish(c, 2, psi, dpsi, REG_GAMMA)
+    assert np.array_equal(bits(psi2), bits(ref["psi"]))
+    check_positions(c, ref, scan2, "route 2 %s" % gid(c.g))
+    assert np.array_equal(bits(scan2), bits(scan1)), "routes 1 and 2 differ"
+    # route 3: the operands ride along with the object step's own column passes (paired gather)
+    S = S_()
+    st = zeros64(nat.ST_WORDS)
+    st[nat.ST_HINT:nat.ST_HINT + 2] = 14.0
+    nat.check(nat.set_option(c.h, b"model", nat.MODEL_GAUSSIAN))
+    nat.check(nat.set_mask(c.h, None, S))
+    nat.check(nat.set_option(c.h, b"trust_order", 0))
+    psi_d, scan_d, prb = c.D(psi), c.scan.clone(), c.prb.clone()
+    grad, grad0, dd = torch.empty_like(psi_d), torch.zeros_like(psi_d), torch.zeros_like(psi_d)
+    nat.check(nat.cg_obj_begin2(c.h, P_(st), P_(psi_d), P_(scan_d), P_(prb), P_(r["ones"]), P_(c.data), S))
+    nat.check(nat.cg_obj_grad(c.h, P_(st), P_(scan_d), P_(prb), P_(c.data), P_(grad), S))
+    nat.check(nat.cg_obj_dir2(c.h, P_(st), 1, P_(scan_d), P_(prb), P_(r["ones"]), P_(c.data), P_(grad), P_(grad0), P_(dd), S))
+    dpsi3 = host(dd)
+    assert np.all(np.isfinite(dpsi3.view(np.float32))) and np.abs(dpsi3).max() > 0
+    gamma3 = float(np.float32(0.25 * np.abs(psi).max() / np.abs(dpsi3).max()))      # a step that moves psi by a quarter at most
+    st[nat.ST_GAMMA_PSI] = gamma3
+    nat.check(nat.cg_obj_finish(c.h, P_(st), 3, P_(psi_d), P_(dd), P_(scan_d), P_(r["ones"]), P_(r["vt"]), P_(r["lz"]),
+                                r["nc"], UPS, float(UP), S))
+    psi3, scan3 = host(psi_d), host(scan_d)
+    nat.check(nat.set_option(c.h, b"trust_order", 0))
+    ref3 = reg_reference(c, psi, dpsi3, gamma3)
+    assert np.array_equal(bits(psi3), bits(ref3["psi"]))
+    check_positions(c, ref3, scan3, "route 3 %s" % gid(c.g))
+    assert np.array_equal(bits(scan3[1:]), bits(P["scan"][1:])), "only angle 0 is corrected"
+    psi31, scan31 = obj_finish(c, 1, psi, dpsi3, gamma3)
+    check_positions(c, ref3, scan31, "route 1 on route 3's operands %s" % gid(c.g))
+    assert np.array_equal(bits(psi31), bits(psi3))
+    print("routes 1 and 3 bit-equal: %s" % np.array_equal(bits(scan31), bits(scan3)))
+    assert np.array_equal(bits(scan31), bits(scan3)), "routes 1 and 3 differ: %s" % (scan31[0] - scan3[0])
+    for s in (2, 3):
+        c.slv.release_work(s)
+
+
+def test_prb_finish(case):
+    """ptycho_cg_prb_finish: probe += float32(state[GAMMA_PRB]) dprb, float32 product then float32 sum, every angle."""
+    nat, P_, S_ = nat_mod()
+    c = case
+    P = c.P
+    if P["ndet"] not in REG_SIZES or P["nscan"] > 100:
+        pytest.skip("the registration tail at 48, 64, 112, 192, 256, 512, 1024")
+    rng = np.random.default_rng(13)
+    dprb = (0.3 * crand(rng, P["prb"].shape)).astype(np.complex64)
+    gamma = 0.37
+    st = zeros64(nat.ST_WORDS)
+    st[nat.ST_GAMMA_PRB] = gamma
+    st[nat.ST_GAMMA_PSI] = 5.0                    # not the word this stage reads
+    prb = c.prb.clone()
+    nat.check(nat.cg_prb_finish(c.h, P_(st), P_(prb), P_(c.D(dprb)), S_()))
+    want = cs.axpy32(P["prb"], dprb, gamma)
+    assert not np.array_equal(bits(want), bits(P["prb"]))
+    assert np.array_equal(bits(host(prb)), bits(want))
