@@ -155,6 +155,43 @@ int ptycho_gauge_fit(double* gauge, const void* psi, const void* ref, const floa
                      size_t n, double* work, void* stream);
 int ptycho_gauge_apply(void* x, const double* gauge, size_t ptheta, size_t ny, size_t nx, int which, void* stream);
 
+/* Fit residuals of a reconstruction per frame and per detector pixel (no handle; libtike.hipfft.fit): how well the
+ * modelled intensity explains the data.  Every launch runs on `stream`, nothing synchronises, no float atomics and fixed
+ * summation orders: the same inputs give the same bits.  ptheta in [1, 65535], nscan and npix below 2^31, ptheta *
+ * nscan * npix at most 2^59.
+ *   ptycho_fit_accumulate  inten (float32 [count]) = |g|^2 (add = 0) or += |g|^2 (add != 0), g complex64 [count],
+ *                          |g|^2 = re * re + im * im in float32, each operation rounded (no fused multiply-add).  One launch.
+ *   ptycho_fit_work_words  float64 words of scratch that ptycho_fit_frames needs (it may be 0: pass any non-null
+ *                          pointer then); at most max(1 MiB, bytes of data / 4) / 8.  0 also for sizes out of range.
+ *   ptycho_fit_frames      one pass over g (complex64 [ptheta][nscan][npix], the farplane of the last or only mode; may be
+ *                          NULL), inten (float32, same shape, the summed intensity of the other modes; may be NULL, not
+ *                          both) and data (float32, same shape), then a second launch that adds the partial sums left
+ *                          in `work` in index order.  Per pixel, in float32: I = (inten ? inten : 0) + (g ? |g|^2 : 0),
+ *                          I' = I * (float)((a/b) * (a/b)) with {a, b} = ab (float64 [2] on the device, as in
+ *                          ptycho_cg_project; NULL: I' = I), d = data; square roots and logarithms are the hardware's
+ *                          (1 ulp), ln x = ln 2 * log2 x.  mask: npix bytes shared by all frames, nonzero = measured, in
+ *                          the layout of ptycho_set_mask's argument; NULL: every pixel is measured.  An unmeasured pixel
+ *                          enters no sum, whatever data, g or inten hold there (NaN and Inf included: a select, not a
+ *                          product); a non-finite value at a measured pixel propagates.
+ *                          frames (float64 [ptheta][nscan][8], written in full): sums over the measured pixels of the
+ *                          frame, terms in float32, accumulated in float64, of
+ *                            0: I'   1: d   2: sqrt(I' d)   3: (sqrt I' - sqrt d)^2   4: I' - d ln(I' + 1e-32)
+ *                            5: d - d ln(d + 1e-32)   6: |sqrt I' - sqrt d|   7: sqrt d
+ *                          (2 and 0 summed over all frames are a and b of the probe rescale; 3 is the gaussian cost,
+ *                          4 the poisson_ml cost as logged, 2 * (4 - 5) the Poisson deviance, 6 / 7 the amplitude
+ *                          R-factor).  pixels (float64 [ptheta][4][npix], written in full; NULL: not wanted): sums over
+ *                          the nscan frames of the angle in index order of
+ *                            0: I'   1: d   2: sqrt I' - sqrt d (signed)   3: (sqrt I' - sqrt d)^2,
+ *                          every map exactly 0 at an unmeasured pixel.  A frame's sums depend on that frame's values
+ *                          alone; frames do not depend on whether pixels is asked for.
+ * PTYCHO_ERR_ARG, before any HIP call, for a null inten / g (accumulate), a null frames / data / work, inten and g both
+ * null, a zero size or sizes out of the range above. */
+int ptycho_fit_accumulate(float* inten, const void* g, size_t count, int add, void* stream);
+size_t ptycho_fit_work_words(size_t ptheta, size_t nscan, size_t npix);
+int ptycho_fit_frames(double* frames, double* pixels, const float* inten, const void* g, const float* data,
+                      const unsigned char* mask, const double* ab, size_t ptheta, size_t nscan, size_t npix,
+                      double* work, void* stream);
+
 /* ---- fused CG-stage entry points ("plus fused CG-stage entry points") ----
  * The elementwise stages of CGPtychoSolver.run (src/libtike/cufft/ptycho.py:325-393) are
  * fused into the row pass of the DFT so that farplanes are never materialised.  The

@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,6 +39,7 @@
 #include "k_modes.hpp"
 #include "k_frc.hpp"
 #include "k_gauge.hpp"
+#include "k_fit.hpp"
 
 using namespace pty;
 
@@ -59,6 +61,7 @@ namespace {
 #include "host_ops.hpp"
 #include "host_cg.hpp"
 #include "host_gauge.hpp"
+#include "host_fit.hpp"
 
 extern "C" {
 
@@ -745,6 +748,35 @@ int ptycho_gauge_apply(void* x, const double* gauge, size_t ptheta, size_t ny, s
     if (ny > kGaugeMaxSide || nx > kGaugeMaxSide || ((nx + 255) / 256) * ny > 0x7fffffffull)
         return fail(PTYCHO_ERR_ARG, "ny or nx too large for one launch");
     return do_gauge_apply((c32*)x, gauge, (int)ptheta, (int)ny, (int)nx, which, (hipStream_t)stream);
+}
+
+// ---- fit residuals per frame and per pixel (k_fit.hpp, libtike.hipfft.fit): no handle --------------------------------------
+int ptycho_fit_accumulate(float* inten, const void* g, size_t count, int add, void* stream) {
+    if (!inten || !g) return fail(PTYCHO_ERR_ARG, "inten and g must not be null");
+    if (count == 0) return fail(PTYCHO_ERR_ARG, "count must be positive");
+    if (count > kFitMaxElems || (count + 1023) / 1024 > 0x7fffffffull)
+        return fail(PTYCHO_ERR_ARG, "count too large for one launch");
+    return do_fit_accumulate(inten, (const c32*)g, count, add, (hipStream_t)stream);
+}
+
+size_t ptycho_fit_work_words(size_t ptheta, size_t nscan, size_t npix) {
+    if (!fit_sizes_ok(ptheta, nscan, npix)) return 0;
+    const FitPlan p = fit_plan((long long)ptheta, (long long)nscan, (long long)npix);
+    return (size_t)(p.fwords + p.pwords);
+}
+
+int ptycho_fit_frames(double* frames, double* pixels, const float* inten, const void* g, const float* data,
+                      const unsigned char* mask, const double* ab, size_t ptheta, size_t nscan, size_t npix,
+                      double* work, void* stream) {
+    if (!frames || !data || !work) return fail(PTYCHO_ERR_ARG, "frames, data and work must not be null");
+    if (!inten && !g) return fail(PTYCHO_ERR_ARG, "inten and g must not both be null");
+    if (ptheta == 0 || nscan == 0 || npix == 0) return fail(PTYCHO_ERR_ARG, "all sizes must be positive");
+    if (ptheta > kFitMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
+    if (!fit_sizes_ok(ptheta, nscan, npix) ||
+        (ptheta * nscan * kFitCols + ptheta * kFitMaps * npix) / 256 + 2 > 0x7fffffffull)
+        return fail(PTYCHO_ERR_ARG, "nscan, npix or their product with ptheta too large for one launch");
+    return do_fit_frames(frames, pixels, inten, (const c32*)g, data, mask, ab, (long long)ptheta, (long long)nscan,
+                         (long long)npix, work, (hipStream_t)stream);
 }
 
 }  // extern "C"

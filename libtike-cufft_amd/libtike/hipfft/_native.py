@@ -29,6 +29,7 @@ SYMBOLS = ("ptycho_create", "ptycho_free", "ptycho_destroy", "ptycho_get",
            "ptycho_set_mask", "ptycho_orthogonalize_modes",
            "ptycho_frc_prepare", "ptycho_frc_rings",
            "ptycho_illumination", "ptycho_gauge_fit", "ptycho_gauge_apply",
+           "ptycho_fit_accumulate", "ptycho_fit_work_words", "ptycho_fit_frames",
            "ptycho_last_error", "ptycho_version")
 
 if not os.path.exists(LIB_PATH):
@@ -103,6 +104,12 @@ gauge_fit = _sig("ptycho_gauge_fit", _i, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp,
 gauge_apply = _sig("ptycho_gauge_apply", _i, _vp, _vp, _sz, _sz, _sz, _i, _vp)
 #: float64 words of ``gauge_fit``'s scratch per angle (PTYCHO_GAUGE_WORK_PER_ANGLE)
 GAUGE_WORK_PER_ANGLE = 16384
+#: fit residuals (no handle): inten, g, count, add, stream
+fit_accumulate = _sig("ptycho_fit_accumulate", _i, _vp, _vp, _sz, _i, _vp)
+#: ptheta, nscan, npix -> float64 words of ``fit_frames``'s scratch (0 for sizes out of range)
+fit_work_words = _sig("ptycho_fit_work_words", _sz, _sz, _sz, _sz)
+#: frames, pixels, inten, g, data, mask, ab, ptheta, nscan, npix, work, stream
+fit_frames = _sig("ptycho_fit_frames", _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp)
 #: ``get`` keys: options "chunk" and "window" as set; ``GET_WORK_SLOT0 + s``: 1 if CG work slot ``s`` holds device memory
 GET_CHUNK, GET_WINDOW, GET_WORK_SLOT0 = 100, 101, 200
 #: ``get`` key: 1 if a measured-pixel mask is set on the handle

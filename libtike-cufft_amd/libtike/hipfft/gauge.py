@@ -106,7 +106,7 @@ def _device(*tensors):
         if t is None:
             continue
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError("libtike.hipfft.gauge works on device tensors; there is no CPU path")
+            raise ValueError("libtike.hipfft works on device tensors; there is no CPU path")
         if dev is not None and t.device != dev:
             raise ValueError("operands live on different devices: %s and %s" % (dev, t.device))
         dev = t.device

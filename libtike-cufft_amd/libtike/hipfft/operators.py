@@ -256,6 +256,47 @@ class PtychoHIP:
         nat.check(nat.fft2(self._h, _ptr(out), _ptr(x), nb, 1 if inverse else -1, _stream()))
         return out
 
+    def residuals(self, data, psi, scan, probe, mask=None, rescale=False):
+        """How well ``(psi, scan, probe)`` explains ``data``, per frame and per detector pixel (``libtike.hipfft.fit``).
+
+        ``probe``: ``[ptheta, M, nprb, nprb]`` or ``[ptheta, nprb, nprb]``, any ``M >= 1``; any detector size of the
+        operators.  One farplane is reused for every mode: ``fwd`` into it, ``accumulate_intensity`` for all modes but the
+        last, then ``fit_frames``.  ``rescale=True`` reports the fit as the next CG iteration would see it: a first pass
+        gives ``a = sum sqrt(I d)`` and ``b = sum I`` on the device, a second pass prices ``I (a / b)^2``.
+
+        Returns the ``fit_frames`` dict (``"frames"``, ``"pixels"``) plus, per frame ``[ptheta, nscan]``,
+        ``"cost_gaussian"``, ``"cost_poisson"``, ``"deviance"``, ``"r_factor"`` and ``"flux_ratio"`` (data over model),
+        and ``"scale"``: ``a / b`` of the unscaled intensity, a 0-dim float64 device tensor.  The inputs are not modified;
+        nothing synchronises.  With a process group the frames are this rank's shard and ``rescale=True`` raises
+        ``NotImplementedError`` (``a`` and ``b`` would have to be summed over the ranks).
+        """
+        from .fit import accumulate_intensity, check_fit_frames, fit_frames   # fit imports this module
+        if rescale and getattr(self, "group", None) is not None:
+            raise NotImplementedError("residuals(rescale=True) on a solver with a process group")
+        if probe.dim() == 3:
+            probe = probe[:, None]
+        if probe.dim() != 4 or probe.shape[1] < 1:
+            raise ValueError("probe must be [ptheta, M, nprb, nprb] or [ptheta, nprb, nprb], got %s" % (tuple(probe.shape),))
+        shape = (self.ptheta, self.nscan, self.ndet, self.ndet)
+        data = self._operand(data, torch.float32, shape, "data")
+        nmodes = probe.shape[1]
+        farplane = torch.empty(shape, dtype=torch.complex64, device=data.device)
+        check_fit_frames(data, farplane, None, mask)
+        inten = None
+        for m in range(nmodes):
+            self.fwd(psi, scan, probe[:, m], out=farplane)
+            if m + 1 < nmodes:
+                inten = accumulate_intensity(farplane, out=inten)
+        fit = fit_frames(data, farplane, inten, mask, None, pixels=not rescale)
+        f = fit["frames"]
+        scale = f[..., 2].sum() / f[..., 0].sum()
+        if rescale:
+            fit = fit_frames(data, farplane, inten, mask, torch.stack((f[..., 2].sum(), f[..., 0].sum())))
+            f = fit["frames"]
+        fit.update(cost_gaussian=f[..., 3], cost_poisson=f[..., 4], deviance=2.0 * (f[..., 4] - f[..., 5]),
+                   r_factor=f[..., 6] / f[..., 7], flux_ratio=f[..., 1] / f[..., 0], scale=scale)
+        return fit
+
     # -- host batching (ptycho.py:70-78, 91-95, 108-111, 125-129) -----------
     def _batch(self, function, output, *inputs):
         """NumPy in / NumPy out, one angular partition of ``ptheta`` views at a
