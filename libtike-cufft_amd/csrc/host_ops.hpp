@@ -55,7 +55,11 @@ int launch_adjwin(ptycho_handle h, ColArgs a, hipStream_t st, int wg_target = 0)
 #endif
     {
         ProfSpan ps(h, K_COLS_ADJ_OBJ, st);
-        hipLaunchKernelGGL((k_cols_adjwin<N, SPLIT, CW>), dim3((unsigned)(a.nstrips * nseg)), dim3(NTHREADS), 0, st, a, seglen);
+        // ndet 256 and 512: overlap-add window in registers (k_cols_adjreg); the other sizes keep the LDS window
+        if constexpr ((N == 256 || N == 512) && CW == 0)
+            hipLaunchKernelGGL((k_cols_adjreg<N, SPLIT>), dim3((unsigned)(a.nstrips * nseg)), dim3(NTHREADS), 0, st, a, seglen);
+        else
+            hipLaunchKernelGGL((k_cols_adjwin<N, SPLIT, CW>), dim3((unsigned)(a.nstrips * nseg)), dim3(NTHREADS), 0, st, a, seglen);
     }
     HIP_TRY(hipGetLastError());
     return PTYCHO_OK;

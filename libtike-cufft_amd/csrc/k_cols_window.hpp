@@ -13,7 +13,7 @@
 // not depend on the order: a position that does not fit the current window
 // flushes it and re-anchors.
 // ---------------------------------------------------------------------------
-constexpr int kBucketPx = 4;   // BX: column bucket of the sort key, and window slack
+// (kBucketPx, the column bucket of the sort key and the window's slack: adjreg_map.hpp)
 
 template <int N>
 struct WinCfg {
@@ -278,6 +278,231 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
     }
     __syncthreads();
     flush(Ybase, Ytop);
+    STAMP(7)
+    STAMP_FLUSH(a.stamps ? a.stamps + 12 : a.stamps)
+}
+
+// ---------------------------------------------------------------------------
+// The same pass with the overlap-add window in REGISTERS (ndet = 256 and 512).  In k_cols_adjwin the combine is a chain of
+// LDS read-modify-writes on the window (35 % of the kernel at 256, profiles/r04/stamps.txt).  Here every window pixel
+// has an owner thread (adjreg_map.hpp: column tid % WC, RPG consecutive rows of group tid / WC), which gathers the four
+// taps of its pixels from the T tile -- independent LDS reads, no LDS write -- and adds them to its accumulators.  The
+// tile carries kBucketPx zero columns on each side and a zero row above and below, and row indices are clamped onto
+// the zero rows, so the combine has no branch.  Groups of rows that have slid out below the current position are
+// retired: added to the object (float atomics, or the fixed-point image; by all threads through a small LDS stage when
+// the window slides by one group, else by their owners) and cleared.  A pixel is
+// retired after the last position of the run that touches it, so the partial sums that reach memory are those of
+// k_cols_adjwin.
+// ---------------------------------------------------------------------------
+template <int N, bool SPLIT = false>
+__global__ __launch_bounds__(Plan<N>::T * ColCfg<N>::C, 2) void k_cols_adjreg(const ColArgs a, const int seglen) {
+    using P = Plan<N>;
+    using F = Fft<P, +1>;
+    constexpr int E = P::E, T = P::T, C = ColCfg<N>::C, NT = T * C;
+    constexpr int LAST = P::NSTEP - 1;
+    using W = AdjRegCfg<N, NT>;
+    static_assert(C == W::C, "strip width");
+    constexpr int WC = W::WC, G = W::G, RPG = W::RPG;
+    // exchange buffer = T tile (W::TILE: zero border, see adjreg_map.hpp); only the tile's own elements are ever written
+    __shared__ c32 lds[W::TILE];
+    // the accumulators take the registers the inter-step twiddles had in k_cols_adjwin: a set is re-read from this copy of
+    // the table right before the step that uses it (same values, k_cols_argmax does the same)
+    __shared__ c32 wtab[N];
+    __shared__ c32 stage[W::STAGE];   // the rows on their way out of a window that slides by one group
+
+    const int tid = threadIdx.x;
+    const int c = tid % C, j0 = tid / C;
+    const int cw = tid % WC, g = tid / WC;   // owned window column and row group (g >= G: none)
+    const int strip = blockIdx.x % a.nstrips, seg = blockIdx.x / a.nstrips;
+    const int x0 = (a.strip0 + strip) * C;
+    const int x = x0 + c;
+    const Geom ge = a.ge;
+    const int ix = x - ge.pad;
+    const bool col_ok = ix >= 0 && ix < ge.nprb;
+    const float cinv = 1.0f / (float)N;
+    const c32 zero = c32{0.0f, 0.0f};
+    const float det_sc = a.det_acc ? det_scale_of(a.det) : 0.0f;   // deterministic option: float -> fixed point
+    auto at = [&](int i) { return (i + 1) * W::P + c + W::COL0; };
+
+    F fft;
+    for (int o = tid; o < N; o += NT) wtab[o] = a.table[o];
+    for (int o = tid; o < W::TILE; o += NT) lds[o] = zero;
+
+    c32 pr[E];   // c * probe strip, natural order (row j0 + m*T); zero on padding
+    int cur_t = -1;
+    c32 acc[RPG];
+#pragma unroll
+    for (int r = 0; r < RPG; ++r) acc[r] = zero;
+    AdjRegWin w{-1, 0, 0, 0};   // uniform across the workgroup
+
+    auto add_to_object = [&](const c32 v, int t, int Y, int X) {   // as the flush of k_cols_adjwin
+        if ((v.x != 0.0f || v.y != 0.0f) && Y < ge.nz && X >= 0 && X < ge.n) {
+            const size_t e = ((size_t)t * ge.nz + Y) * ge.n + X;
+            if (a.det_acc) {
+                atomicAdd(reinterpret_cast<unsigned long long*>(a.det_acc + 2 * e), (unsigned long long)__float2ll_rn(v.x * det_sc));
+                atomicAdd(reinterpret_cast<unsigned long long*>(a.det_acc + 2 * e + 1), (unsigned long long)__float2ll_rn(v.y * det_sc));
+            } else {
+                float* op = reinterpret_cast<float*>(a.dst + e);
+                atomicAdd(op, v.x);
+                atomicAdd(op + 1, v.y);
+            }
+        }
+    };
+    // Retire of the nret oldest groups by their owners (re-anchor and end of the run: all G; a slide by more than SG groups).
+    auto retire = [&](int nret) {
+        if (w.t < 0 || g >= G || adjreg_rank<W>(w, g) >= nret) return;
+        const int Y0 = adjreg_row0<W>(w, g), X = w.X0 + cw;
+#pragma unroll
+        for (int r = 0; r < RPG; ++r) {
+            add_to_object(acc[r], w.t, Y0 + r, X);
+            acc[r] = zero;
+        }
+    };
+    // Retire of a slide, first half: the owners of the nret <= SG oldest groups move them to the stage.  Second half, after
+    // the position's barrier: ALL threads add the staged rows to the object.  The stage is written again at a later position
+    // only, behind that position's "previous combine done" barrier.
+    auto stage_groups = [&](int nret) {
+        if (g >= G) return;
+        const int rank = adjreg_rank<W>(w, g);
+        if (rank >= nret) return;
+#pragma unroll
+        for (int r = 0; r < RPG; ++r) {
+            stage[adjreg_stage_slot<W>(rank, r, cw)] = acc[r];
+            acc[r] = zero;
+        }
+    };
+
+    const int kb = a.k_begin + seg * seglen;
+    const int ke = kb + seglen < a.k_end ? kb + seglen : a.k_end;
+
+    __shared__ RunMeta rm;
+    load_run(rm, a.order, a.scan, kb, ke, tid);
+    struct St { int p, t; Pos q; bool have; };
+    auto decode = [&](int k) -> St {
+        St st;
+        st.have = k < ke;
+        st.p = 0; st.t = 0; st.q = Pos{0, 0, 0.f, 0.f, false, false};
+        if (!st.have) return st;
+        st.p = uni_i(rm.p[k - kb]);
+        st.t = st.p / ge.nscan;
+        st.q = decode_xy(uni_f(rm.py[k - kb]), uni_f(rm.px[k - kb]), ge);
+        return st;
+    };
+    auto tile_of = [&](const St& st, int k) {
+        return a.src + (size_t)(a.natural_tiles ? st.p : (k - a.k_begin)) * N * N;
+    };
+
+    __syncthreads();
+    STAMP_DECL
+    St st = decode(kb);
+    c32 v[E];
+    if (st.have && st.q.valid) {
+        const c32* tile_in = tile_of(st, kb);
+        if (a.nt & 8)
+            fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return __builtin_nontemporal_load(tile_in + (size_t)i * N + x); });
+        else
+            fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
+    }
+    for (int k = kb; k < ke; ++k) {
+        St nx = decode(k + 1);
+        if (!st.q.valid) {   // skipped position: nothing to add; fetch the next tile
+            if (nx.have && nx.q.valid) {
+                const c32* tile_in = tile_of(nx, k + 1);
+                fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
+            }
+            st = nx;
+            continue;
+        }
+        const Pos q = st.q;
+        int jz = j0;
+        asm volatile("" : "+v"(jz));   // opaque copy: keeps the twiddle reads inside the position loop
+        if (st.t != cur_t) {
+            const c32* prb = a.aux + (size_t)st.t * ge.nprb * ge.nprb;
+#pragma unroll
+            for (int m = 0; m < E; ++m) {
+                const int iy = j0 + m * T - ge.pad;
+                const bool ok = col_ok && iy >= 0 && iy < ge.nprb;
+                const c32 pw = prb[ok ? ((size_t)iy * ge.nprb + ix) : 0];
+                pr[m] = ok ? pw * cinv : zero;
+            }
+            cur_t = st.t;
+        }
+        // ---- inverse DFT over y of this strip (tile already in v) ----------------------
+        STAMP(0)          // loop head, decode, probe strip
+        STAMP_DRAIN();
+        STAMP(1)          // wait for the tile loads
+        if (SPLIT) {
+            fft.template init_step<LAST>(jz, wtab);
+            fft.template compute<LAST>(v);   // twiddle + radix 16: the step k_rows_split left
+        } else {
+            fft.template compute<0>(v);
+            if (P::NSTEP > 1) {
+                fft.template store<0>(v, j0, [&](int i, c32 val) { lds[at(i)] = val; });
+                __syncthreads();
+                fft.template load<1>(v, j0, [&](int i) { return lds[at(i)]; });
+                if (P::NSTEP > 2) {
+                    __syncthreads();
+                    if constexpr (P::NSTEP > 2) fft.template init_step<1>(jz, wtab);
+                    fft.template compute<1>(v);
+                    fft.template store<1>(v, j0, [&](int i, c32 val) { lds[at(i)] = val; });
+                    __syncthreads();
+                    fft.template load<2>(v, j0, [&](int i) { return lds[at(i)]; });
+                }
+                if constexpr (P::NSTEP > 1) fft.template init_step<LAST>(jz, wtab);
+                fft.template compute<LAST>(v);
+            }
+        }
+        // ---- T[y][c] = conj(c * prb) * near, written over the slots this thread just read ----
+        {
+            c32 nat[E];
+            F::to_natural(v, nat);
+#pragma unroll
+            for (int m = 0; m < E; ++m) {
+                const c32 pw = pr[m];
+                nat[m] = c32{pw.x * nat[m].x + pw.y * nat[m].y, pw.x * nat[m].y - pw.y * nat[m].x};
+            }
+            // split kernel: no exchange went through the tile, so the "previous combine is done"
+            // barrier sits here, after this position's transform, instead of at the end of the loop
+            STAMP(2)      // transform + probe product
+            if (SPLIT) __syncthreads();
+            STAMP(3)      // barrier: previous combine done
+#pragma unroll
+            for (int m = 0; m < E; ++m) lds[at(j0 + m * T)] = nat[m];
+        }
+        STAMP(8)          // T store
+        // prefetch the next tile while the combine runs
+        if (nx.have && nx.q.valid) {
+            const c32* tile_in = tile_of(nx, k + 1);
+            if (a.nt & 8)
+                fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return __builtin_nontemporal_load(tile_in + (size_t)i * N + x); });
+            else
+                fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
+        }
+        STAMP(9)          // prefetch issue
+        // ---- window bookkeeping (workgroup-uniform) and retire: registers only, no barrier ----
+        const int Xa = q.sx + x0 - ge.pad;   // object column of strip column cc = 0
+        const int nret = adjreg_retire_count<W>(w, st.t, Xa, q.sy);
+        const AdjRegWin was = w;
+        int nstaged = 0;
+        if (nret > 0) {
+            if (nret <= W::SG) {
+                stage_groups(nret);
+                nstaged = nret;
+            } else {
+                retire(nret);
+            }
+            adjreg_advance<W>(w, nret, st.t, q.sx, q.sy, x0 - ge.pad);
+        }
+        STAMP(4)          // window bookkeeping, retire
+        __syncthreads();   // T tile complete, staged rows visible
+        STAMP(5)          // barrier: T tile complete
+        for (int o = tid; o < nstaged * RPG * WC; o += NT) add_to_object(stage[o], was.t, was.Ybase + o / WC, was.X0 + o % WC);
+        if (g < G) adjreg_combine<W>(acc, lds, w, g, cw, Xa, q.sy, ge.pad, q.fy, q.fx);
+        STAMP(6)          // combine
+        if (!SPLIT) __syncthreads();   // combine done: the tile may be overwritten by the next position
+        st = nx;
+    }
+    retire(G);
     STAMP(7)
     STAMP_FLUSH(a.stamps ? a.stamps + 12 : a.stamps)
 }

@@ -12,7 +12,7 @@
 //   fwd : k_cols_gatherwin<FWD>  object rows cached in LDS -> bilerp * probe -> DFT over y -> strip of g
 //         k_rows                 in-place DFT over x on g (zero columns are never read)
 //   adj : k_rows                 inverse DFT over x, g -> chunk scratch (g untouched)
-//         k_cols_adjwin          inverse DFT over y -> conj(probe) -> LDS overlap-add window -> f   (object)
+//         k_cols_adjreg / adjwin inverse DFT over y -> conj(probe) -> overlap-add window (registers at 256 / 512, else LDS) -> f   (object)
 //         k_cols_gatherwin<ADJ_PRB>                  -> conj(patch) -> probe accumulators -> prb    (probe)
 //   ndet <= 128: the tile fits a CU's LDS and both passes run in one launch (k_tile.hpp); ndet = 256: one radix-16 step
 //   of the DFT over y moves into the row pass ("split"); k_cols<MODE> is the un-windowed path (option window = 0,
@@ -36,6 +36,7 @@
 
 #include "../../include/ptycho_hip.h"
 #include "fft_core.hpp"
+#include "adjreg_map.hpp"
 #include "k_modes.hpp"
 #include "k_frc.hpp"
 #include "k_gauge.hpp"

@@ -30,8 +30,8 @@ torch.cuda.synchronize()
 prof = slv.profile_read()
 assert dbg(slv._h, buf) == 0
 names = {0: ["loop head", "gather (LDS taps + weights)", "probe product + radix-16", "store issue", "barrier A", "window update", "barrier B", "-", "-", "-", "-", "-"],
-         1: ["loop head / probe strip", "wait for tile loads", "radix-16 + probe product", "barrier (prev. combine done)", "window bookkeeping + flush", "barrier (T complete)", "combine", "final flush", "T store", "prefetch issue", "-", "-"]}
-for role, title in ((0, "k_cols_gatherwin<%d,FWD%s>" % (ND, ",split" if ND == 256 else "")), (1, "k_cols_adjwin<%d%s>" % (ND, ",split" if ND == 256 else ""))):
+         1: ["loop head / probe strip", "wait for tile loads", "radix-16 + probe product", "barrier (prev. combine done)", "window bookkeeping + retire", "barrier (T complete)", "staged rows to the object + combine", "final retire", "T store", "prefetch issue", "-", "-"]}
+for role, title in ((0, "k_cols_gatherwin<%d,FWD%s>" % (ND, ",split" if ND == 256 else "")), (1, "k_cols_adjreg<%d%s>" % (ND, ",split" if ND == 256 else ""))):
     v = np.array([buf[12 * role + i] for i in range(12)], dtype=np.float64)
     tot = v.sum()
     print(title, " total wave-cycles per launch %.3e" % (tot / reps))
