@@ -192,6 +192,44 @@ int ptycho_fit_frames(double* frames, double* pixels, const float* inten, const 
                       const unsigned char* mask, const double* ab, size_t ptheta, size_t nscan, size_t npix,
                       double* work, void* stream);
 
+/* Raw detector frames to the solver's data (no handle; libtike.hipfft.prepare): crop, bin, dark, gain, bad pixels, clip,
+ * scale, ifftshift and statistics in one pass that reads every raw byte once, then a second launch that combines the
+ * partial results left in `work` in index order.  Runs on `stream`, nothing synchronises, no atomics and fixed summation
+ * orders: the same inputs give the same bits.
+ *   raw    frames [ptheta][nraw][H][W], stored centred; dtype 0 uint16, 1 uint32, 2 int32, 3 float32.
+ *   index  int64 [ptheta][nscan] on the device or NULL: output frame j reads raw frame index[t][j] (NULL: frame j, and
+ *          nraw must equal nscan).  An index outside [0, nraw) gives an all-zero frame and four zero statistics; nothing
+ *          is read out of bounds for it.
+ *   dark, gain  float32 [H][W] or NULL (0 and 1).  bad: uint8 [H][W] or NULL, nonzero = bad.
+ *   y0, x0 raw row and column of the first pixel of the crop window; they may be negative or leave part of the window
+ *          outside the frame.  bin: 1, 2 or 4.  ndet: any size in [1, 32768].
+ * Centred pixel (oy, ox) covers the raw pixels (y0 + oy bin + by, x0 + ox bin + bx), by, bx < bin.  It is MEASURED if all
+ * of them lie inside the frame and none is bad (the same for every frame).  In float32, every operation rounded (no
+ * fused multiply-add): t = ((float)raw - dark) * gain per raw pixel; v = sum of t in the order by outer, bx inner from
+ * the first term; clip != 0: v = v < 0 ? 0 : v (a NaN stays); v = v * scale; an unmeasured pixel gets v = 0 by a select,
+ * whatever raw, dark and gain hold there (NaN and Inf included).  A non-finite value at a measured pixel reaches that
+ * pixel and that frame's sums only.
+ *   data   float32 [ptheta][nscan][ndet][ndet] in the operators' layout: data[r][c] = v[(r + ndet/2) % ndet][(c + ndet/2)
+ *          % ndet] (ifftshift: centred pixel ndet/2 lands at [0][0]; for even ndet this is also fftshift).
+ *   mask   uint8 [ndet][ndet], same layout, 1 = measured: the argument of ptycho_set_mask.
+ *   frames float64 [ptheta][nscan][4], over the measured pixels of the frame: 0 sum of v, 1 sum of v * v (the product
+ *          rounded in float32, both sums accumulated in float64), 2 max of v (fmaxf from -inf: a NaN is skipped; -inf
+ *          without a measured pixel), 3 the number of raw pixels of measured bins with (float)raw >= saturation (a NaN
+ *          saturation disables the count).
+ *   pixels float64 [ptheta][4][ndet][ndet] or NULL, layout of data: the same four over the frames of the angle whose
+ *          index is in range; map 3 counts the frames in which any raw pixel of the bin was saturated; every map is 0
+ *          at an unmeasured pixel.
+ *   work   float64 scratch of ptycho_prepare_work_words(ptheta, nscan, ndet * ndet) words (it may be 0: pass any
+ *          non-null pointer then; 0 also for sizes out of range).
+ * PTYCHO_ERR_ARG, before any HIP call, for a null data / mask / frames / raw / work, a zero size, bin outside {1, 2, 4},
+ * an unknown dtype, ptheta > 65535, index NULL with nraw != nscan, ndet > 32768, nraw or nscan or H * W at or above 2^31,
+ * |y0| or |x0| above 2^30, or more than 2^59 elements of raw or data. */
+size_t ptycho_prepare_work_words(size_t ptheta, size_t nscan, size_t npix);
+int ptycho_prepare_frames(float* data, unsigned char* mask, double* frames, double* pixels, const void* raw, int dtype,
+                          const long long* index, const float* dark, const float* gain, const unsigned char* bad,
+                          size_t ptheta, size_t nraw, size_t nscan, size_t H, size_t W, long long y0, long long x0,
+                          int bin, size_t ndet, float saturation, float scale, int clip, double* work, void* stream);
+
 /* ---- fused CG-stage entry points ("plus fused CG-stage entry points") ----
  * The elementwise stages of CGPtychoSolver.run (src/libtike/cufft/ptycho.py:325-393) are
  * fused into the row pass of the DFT so that farplanes are never materialised.  The

@@ -41,6 +41,7 @@
 #include "k_frc.hpp"
 #include "k_gauge.hpp"
 #include "k_fit.hpp"
+#include "k_prepare.hpp"
 
 using namespace pty;
 
@@ -63,6 +64,7 @@ namespace {
 #include "host_cg.hpp"
 #include "host_gauge.hpp"
 #include "host_fit.hpp"
+#include "host_prepare.hpp"
 
 extern "C" {
 
@@ -778,6 +780,35 @@ int ptycho_fit_frames(double* frames, double* pixels, const float* inten, const 
         return fail(PTYCHO_ERR_ARG, "nscan, npix or their product with ptheta too large for one launch");
     return do_fit_frames(frames, pixels, inten, (const c32*)g, data, mask, ab, (long long)ptheta, (long long)nscan,
                          (long long)npix, work, (hipStream_t)stream);
+}
+
+// ---- raw detector frames to solver data (k_prepare.hpp, libtike.hipfft.prepare): no handle -------------------------------
+size_t ptycho_prepare_work_words(size_t ptheta, size_t nscan, size_t npix) {
+    if (!prep_sizes_ok(ptheta, nscan, npix)) return 0;
+    const PrepPlan p = prep_plan((long long)ptheta, (long long)nscan, (long long)npix);
+    return (size_t)(p.fwords + p.pwords);
+}
+
+int ptycho_prepare_frames(float* data, unsigned char* mask, double* frames, double* pixels, const void* raw, int dtype,
+                          const long long* index, const float* dark, const float* gain, const unsigned char* bad,
+                          size_t ptheta, size_t nraw, size_t nscan, size_t H, size_t W, long long y0, long long x0,
+                          int bin, size_t ndet, float saturation, float scale, int clip, double* work, void* stream) {
+    if (!data || !mask || !frames || !raw || !work)
+        return fail(PTYCHO_ERR_ARG, "data, mask, frames, raw and work must not be null");
+    if (ptheta == 0 || nraw == 0 || nscan == 0 || H == 0 || W == 0 || ndet == 0)
+        return fail(PTYCHO_ERR_ARG, "all sizes must be positive");
+    if (bin != 1 && bin != 2 && bin != 4) return fail(PTYCHO_ERR_ARG, "bin must be 1, 2 or 4");
+    if (dtype < 0 || dtype >= kPrepDtypes)
+        return fail(PTYCHO_ERR_ARG, "dtype must be 0 (uint16), 1 (uint32), 2 (int32) or 3 (float32)");
+    if (ptheta > kPrepMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
+    if (!index && nraw != nscan) return fail(PTYCHO_ERR_ARG, "without an index nraw must equal nscan");
+    if (ndet > kPrepMaxNdet || !prep_sizes_ok(ptheta, nscan, ndet * ndet) || !prep_raw_ok(ptheta, nraw, H, W) ||
+        y0 < -kPrepMaxOrigin || y0 > kPrepMaxOrigin || x0 < -kPrepMaxOrigin || x0 > kPrepMaxOrigin ||
+        (ptheta * nscan * kPrepCols + ptheta * kPrepMaps * ndet * ndet) / 256 + 2 > 0x7fffffffull)
+        return fail(PTYCHO_ERR_ARG, "sizes, window origin or their products too large for one launch");
+    const PrepGeom g{(long long)H, (long long)W, y0, x0, bin, (int)ndet};
+    return do_prepare_frames(data, mask, frames, pixels, raw, dtype, index, dark, gain, bad, (long long)ptheta,
+                             (long long)nraw, (long long)nscan, g, saturation, scale, clip, work, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -5,4 +5,5 @@ from libtike.hipfft.ptycho import *  # noqa: F401,F403
 from libtike.hipfft.frc import frc  # noqa: F401
 from libtike.hipfft.gauge import illumination, fit_gauge, apply_gauge, fix_gauge  # noqa: F401
 from libtike.hipfft.fit import fit_frames, accumulate_intensity, flag_frames  # noqa: F401
+from libtike.hipfft.prepare import prepare_frames, initial_probe  # noqa: F401
 from libtike.hipfft import __version__  # noqa: F401

@@ -30,6 +30,7 @@ SYMBOLS = ("ptycho_create", "ptycho_free", "ptycho_destroy", "ptycho_get",
            "ptycho_frc_prepare", "ptycho_frc_rings",
            "ptycho_illumination", "ptycho_gauge_fit", "ptycho_gauge_apply",
            "ptycho_fit_accumulate", "ptycho_fit_work_words", "ptycho_fit_frames",
+           "ptycho_prepare_work_words", "ptycho_prepare_frames",
            "ptycho_last_error", "ptycho_version")
 
 if not os.path.exists(LIB_PATH):
@@ -110,6 +111,14 @@ fit_accumulate = _sig("ptycho_fit_accumulate", _i, _vp, _vp, _sz, _i, _vp)
 fit_work_words = _sig("ptycho_fit_work_words", _sz, _sz, _sz, _sz)
 #: frames, pixels, inten, g, data, mask, ab, ptheta, nscan, npix, work, stream
 fit_frames = _sig("ptycho_fit_frames", _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp)
+#: frame preparation (no handle): ptheta, nscan, npix -> float64 words of ``prepare_frames``'s scratch (0: out of range)
+prepare_work_words = _sig("ptycho_prepare_work_words", _sz, _sz, _sz, _sz)
+#: data, mask, frames, pixels, raw, dtype, index, dark, gain, bad, ptheta, nraw, nscan, H, W, y0, x0, bin, ndet,
+#: saturation, scale, clip, work, stream
+prepare_frames = _sig("ptycho_prepare_frames", _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz,
+                      _ll, _ll, _i, _sz, ctypes.c_float, ctypes.c_float, _i, _vp, _vp)
+#: ``dtype`` codes of ``prepare_frames``'s raw frames
+PREPARE_DTYPES = {"uint16": 0, "uint32": 1, "int32": 2, "float32": 3}
 #: ``get`` keys: options "chunk" and "window" as set; ``GET_WORK_SLOT0 + s``: 1 if CG work slot ``s`` holds device memory
 GET_CHUNK, GET_WINDOW, GET_WORK_SLOT0 = 100, 101, 200
 #: ``get`` key: 1 if a measured-pixel mask is set on the handle
