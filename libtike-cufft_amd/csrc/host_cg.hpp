@@ -181,19 +181,14 @@ int launch_gatherwin_modes(ptycho_handle h, ColArgs a, hipStream_t st) {
     constexpr int NTHREADS = Plan<N>::T * (CW ? CW : ColCfg<N>::C);
     const int np = a.k_end - a.k_begin;
     if (np <= 0 || a.nstrips <= 0) return PTYCHO_OK;
-    int nseg = (h->n_cu * 4 + a.nstrips - 1) / a.nstrips;
-    if (nseg < 1) nseg = 1;
-    int seglen = (np + nseg - 1) / nseg;
-    if (seglen < min_seglen(np, a.nstrips, h->n_cu)) seglen = min_seglen(np, a.nstrips, h->n_cu);
-    if (seglen > kRunMax) seglen = kRunMax;
-    nseg = (np + seglen - 1) / seglen;
+    const RunSplit rs = split_runs(np, a.nstrips, h->n_cu * 4, min_seglen(np, a.nstrips, h->n_cu));
     a.nt = 0;
 #ifdef PTY_STAMPS
     a.stamps = h->stamps;
 #endif
     {
         ProfSpan ps(h, K_COLS_FWD, st);
-        hipLaunchKernelGGL((k_cols_gatherwin<N, M_FWD, false, NM, CW>), dim3((unsigned)(a.nstrips * nseg)), dim3(NTHREADS), 0, st, a, seglen);
+        hipLaunchKernelGGL((k_cols_gatherwin<N, M_FWD, false, NM, CW>), dim3((unsigned)(a.nstrips * rs.nseg)), dim3(NTHREADS), 0, st, a, rs.seglen);
     }
     HIP_TRY(hipGetLastError());
     return PTYCHO_OK;

@@ -8,10 +8,7 @@ namespace {
 // runs of 16) take shorter runs, down to 4: a workgroup's positions are processed one after the other (~5 us each)
 static int min_seglen(int np = 1 << 30, int nstrips = 1, int n_cu = 256) {
     static const int v = exp_env("PTYCHO_HIP_MINSEG", 16);
-    int m = v < 1 ? 1 : v;
-    const long long fill = (long long)np * nstrips / (n_cu > 0 ? n_cu : 1);   // run length that gives one workgroup per CU
-    if (fill < m) m = fill < 4 ? 4 : (int)fill;
-    return m;
+    return min_run(np, nstrips, n_cu, v);
 }
 
 template <int N, int DIR, int MODE>
@@ -42,12 +39,7 @@ int launch_adjwin(ptycho_handle h, ColArgs a, hipStream_t st, int wg_target = 0)
     // ndet 256: two rounds of resident workgroups (one round of runs of 128: within 1 %, six or eight rounds: +4 %);
     // ndet 128: ONE round (two workgroups per CU, runs of 32 positions): 0.234 -> 0.197 ms at 4096 x 128^2; 64 and 32: no gain / worse
     if (wg_target <= 0) wg_target = h->n_cu * (N == 128 ? 2 : 4);   // (512: runs of 128 instead of 64 positions: 1.728 -> 1.709 ms, profiles/r04/stamps.txt)
-    int nseg = (wg_target + a.nstrips - 1) / a.nstrips;
-    if (nseg < 1) nseg = 1;
-    int seglen = (np + nseg - 1) / nseg;
-    if (seglen < min_seglen(np, a.nstrips, h->n_cu)) seglen = min_seglen(np, a.nstrips, h->n_cu);
-    if (seglen > kRunMax) seglen = kRunMax;
-    nseg = (np + seglen - 1) / seglen;
+    const RunSplit rs = split_runs(np, a.nstrips, wg_target, min_seglen(np, a.nstrips, h->n_cu));
     static const int nt_mode_a = exp_env("PTYCHO_HIP_NT", 0);
     a.nt = nt_mode_a;
 #ifdef PTY_STAMPS
@@ -57,9 +49,9 @@ int launch_adjwin(ptycho_handle h, ColArgs a, hipStream_t st, int wg_target = 0)
         ProfSpan ps(h, K_COLS_ADJ_OBJ, st);
         // ndet 256 and 512: overlap-add window in registers (k_cols_adjreg); the other sizes keep the LDS window
         if constexpr ((N == 256 || N == 512) && CW == 0)
-            hipLaunchKernelGGL((k_cols_adjreg<N, SPLIT>), dim3((unsigned)(a.nstrips * nseg)), dim3(NTHREADS), 0, st, a, seglen);
+            hipLaunchKernelGGL((k_cols_adjreg<N, SPLIT>), dim3((unsigned)(a.nstrips * rs.nseg)), dim3(NTHREADS), 0, st, a, rs.seglen);
         else
-            hipLaunchKernelGGL((k_cols_adjwin<N, SPLIT, CW>), dim3((unsigned)(a.nstrips * nseg)), dim3(NTHREADS), 0, st, a, seglen);
+            hipLaunchKernelGGL((k_cols_adjwin<N, SPLIT, CW>), dim3((unsigned)(a.nstrips * rs.nseg)), dim3(NTHREADS), 0, st, a, rs.seglen);
     }
     HIP_TRY(hipGetLastError());
     return PTYCHO_OK;
@@ -73,19 +65,14 @@ int launch_gatherwin(ptycho_handle h, ColArgs a, hipStream_t st, int wg_target =
     // whole rounds of resident workgroups (two per CU un-split, three split): a ragged last round costs 5-20 % (round 3: 1.5
     // rounds of the un-split forward pass made the CG iteration 8.43 -> 8.87 ms; one long round 8.49)
     if (wg_target <= 0) wg_target = h->n_cu * (SPLIT ? 6 : 4);
-    int nseg = (wg_target + a.nstrips - 1) / a.nstrips;
-    if (nseg < 1) nseg = 1;
-    int seglen = (np + nseg - 1) / nseg;
-    if (seglen < min_seglen(np, a.nstrips, h->n_cu)) seglen = min_seglen(np, a.nstrips, h->n_cu);
-    if (seglen > kRunMax) seglen = kRunMax;
-    nseg = (np + seglen - 1) / seglen;
+    RunSplit rs = split_runs(np, a.nstrips, wg_target, min_seglen(np, a.nstrips, h->n_cu));
 #ifdef PTYCHO_EXPERIMENTS
     {   // experiment knob: fewer, longer runs
         const int want = exp_env("PTYCHO_HIP_COLSEGS", 0);
         if (want > 0) {
-            seglen = (np + want - 1) / want;
-            if (seglen > kRunMax) seglen = kRunMax;
-            nseg = (np + seglen - 1) / seglen;
+            rs.seglen = (np + want - 1) / want;
+            if (rs.seglen > kRunMax) rs.seglen = kRunMax;
+            rs.nseg = (np + rs.seglen - 1) / rs.seglen;
         }
     }
 #endif
@@ -96,7 +83,7 @@ int launch_gatherwin(ptycho_handle h, ColArgs a, hipStream_t st, int wg_target =
 #endif
     {
         ProfSpan ps(h, MODE == M_FWD ? K_COLS_FWD : K_COLS_ADJ_PRB, st);
-        hipLaunchKernelGGL((k_cols_gatherwin<N, MODE, SPLIT, 1, CW>), dim3((unsigned)(a.nstrips * nseg)), dim3(NTHREADS), 0, st, a, seglen);
+        hipLaunchKernelGGL((k_cols_gatherwin<N, MODE, SPLIT, 1, CW>), dim3((unsigned)(a.nstrips * rs.nseg)), dim3(NTHREADS), 0, st, a, rs.seglen);
     }
     HIP_TRY(hipGetLastError());
     return PTYCHO_OK;
@@ -532,14 +519,9 @@ int do_adj_generic(ptycho_handle h, c32* f, const c32* g, const float* scan, c32
             ca.k_begin = (int)k0; ca.k_end = (int)k1; ca.strip0 = 0; ca.nstrips = (ge.nprb + 15) / 16;
             ca.det_acc = det.det_acc; ca.det = det.det;
             const int np = (int)(k1 - k0);
-            int nseg = (h->n_cu * 4 + ca.nstrips - 1) / ca.nstrips;
-            if (nseg < 1) nseg = 1;
-            int seglen = (np + nseg - 1) / nseg;
-            if (seglen < min_seglen(np, ca.nstrips, h->n_cu)) seglen = min_seglen(np, ca.nstrips, h->n_cu);
-            if (seglen > kRunMax) seglen = kRunMax;
-            nseg = (np + seglen - 1) / seglen;
+            const RunSplit rs = split_runs(np, ca.nstrips, h->n_cu * 4, min_seglen(np, ca.nstrips, h->n_cu));
             ProfSpan ps(h, K_COLS_ADJ_OBJ, st);
-            hipLaunchKernelGGL(k_adjwin_generic, dim3((unsigned)(ca.nstrips * nseg)), dim3(256), win_bytes, st, ca, seglen);
+            hipLaunchKernelGGL(k_adjwin_generic, dim3((unsigned)(ca.nstrips * rs.nseg)), dim3(256), win_bytes, st, ca, rs.seglen);
         } else if (flg == 0) {
             const long long npix = (k1 - k0) * ge.nprb * ge.nprb;
             ProfSpan ps(h, K_COLS_ADJ_OBJ, st);

@@ -77,15 +77,7 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
             const int X = X0 + col;
             if ((v.x != 0.0f || v.y != 0.0f) && Y < ge.nz && X >= 0 && X < ge.n) {
                 const size_t e = ((size_t)t_w * ge.nz + Y) * ge.n + X;
-                if (a.det_acc) {
-                    const float sc = det_sc;
-                    atomicAdd(reinterpret_cast<unsigned long long*>(a.det_acc + 2 * e), (unsigned long long)__float2ll_rn(v.x * sc));
-                    atomicAdd(reinterpret_cast<unsigned long long*>(a.det_acc + 2 * e + 1), (unsigned long long)__float2ll_rn(v.y * sc));
-                } else {
-                    float* op = reinterpret_cast<float*>(a.dst + e);
-                    atomicAdd(op, v.x);
-                    atomicAdd(op + 1, v.y);
-                }
+                accum_c32(a.dst, a.det_acc, det_sc, e, v);
             }
         }
     };
@@ -95,31 +87,16 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
     constexpr int NITEM = (C + 1) * NRG;
     const int rpt = (ge.nprb + 1 + NRG - 1) / NRG;              // output rows per item
 
-    const int kb = a.k_begin + seg * seglen;
-    const int ke = kb + seglen < a.k_end ? kb + seglen : a.k_end;
-
+    const RunBounds rb = run_bounds(a, seg, seglen);
+    const int kb = rb.kb, ke = rb.ke;
     __shared__ RunMeta rm;
     load_run(rm, a.order, a.scan, kb, ke, tid);
-    struct St { int p, t; Pos q; bool have; };
-    auto decode = [&](int k) -> St {
-        St st;
-        st.have = k < ke;
-        st.p = 0; st.t = 0; st.q = Pos{0, 0, 0.f, 0.f, false, false};
-        if (!st.have) return st;
-        st.p = uni_i(rm.p[k - kb]);
-        st.t = st.p / ge.nscan;
-        st.q = decode_xy(uni_f(rm.py[k - kb]), uni_f(rm.px[k - kb]), ge);
-        return st;
-    };
-    auto tile_of = [&](const St& st, int k) {
-        // (object-space bands -- a workgroup owns 16 OBJECT columns -- would read row pieces that straddle two 128-byte lines and
-        // reload the probe strip for every position: both priced and refuted, profiles/r04/adjwin_ablations.txt)
-        return a.src + (size_t)(a.natural_tiles ? st.p : (k - a.k_begin)) * N * N;
-    };
+    auto decode = [&](int k) { return run_decode(rm, k, kb, ke, ge); };
+    auto tile_of = [&](const RunSt& st, int k) { return run_tile<N>(a, st.p, k); };
 
     __syncthreads();
     STAMP_DECL
-    St st = decode(kb);
+    RunSt st = decode(kb);
     c32 v[E];
     if (st.have && st.q.valid) {
         const c32* tile_in = tile_of(st, kb);
@@ -129,7 +106,7 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
             fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
     }
     for (int k = kb; k < ke; ++k) {
-        St nx = decode(k + 1);
+        RunSt nx = decode(k + 1);
         if (!st.q.valid) {   // skipped position: nothing to add; fetch the next tile
             if (nx.have && nx.q.valid) {
                 const c32* tile_in = tile_of(nx, k + 1);
@@ -336,17 +313,8 @@ __global__ __launch_bounds__(Plan<N>::T * ColCfg<N>::C, 2) void k_cols_adjreg(co
     AdjRegWin w{-1, 0, 0, 0};   // uniform across the workgroup
 
     auto add_to_object = [&](const c32 v, int t, int Y, int X) {   // as the flush of k_cols_adjwin
-        if ((v.x != 0.0f || v.y != 0.0f) && Y < ge.nz && X >= 0 && X < ge.n) {
-            const size_t e = ((size_t)t * ge.nz + Y) * ge.n + X;
-            if (a.det_acc) {
-                atomicAdd(reinterpret_cast<unsigned long long*>(a.det_acc + 2 * e), (unsigned long long)__float2ll_rn(v.x * det_sc));
-                atomicAdd(reinterpret_cast<unsigned long long*>(a.det_acc + 2 * e + 1), (unsigned long long)__float2ll_rn(v.y * det_sc));
-            } else {
-                float* op = reinterpret_cast<float*>(a.dst + e);
-                atomicAdd(op, v.x);
-                atomicAdd(op + 1, v.y);
-            }
-        }
+        if ((v.x != 0.0f || v.y != 0.0f) && Y < ge.nz && X >= 0 && X < ge.n)
+            accum_c32(a.dst, a.det_acc, det_sc, ((size_t)t * ge.nz + Y) * ge.n + X, v);
     };
     // Retire of the nret oldest groups by their owners (re-anchor and end of the run: all G; a slide by more than SG groups).
     auto retire = [&](int nret) {
@@ -372,29 +340,16 @@ __global__ __launch_bounds__(Plan<N>::T * ColCfg<N>::C, 2) void k_cols_adjreg(co
         }
     };
 
-    const int kb = a.k_begin + seg * seglen;
-    const int ke = kb + seglen < a.k_end ? kb + seglen : a.k_end;
-
+    const RunBounds rb = run_bounds(a, seg, seglen);
+    const int kb = rb.kb, ke = rb.ke;
     __shared__ RunMeta rm;
     load_run(rm, a.order, a.scan, kb, ke, tid);
-    struct St { int p, t; Pos q; bool have; };
-    auto decode = [&](int k) -> St {
-        St st;
-        st.have = k < ke;
-        st.p = 0; st.t = 0; st.q = Pos{0, 0, 0.f, 0.f, false, false};
-        if (!st.have) return st;
-        st.p = uni_i(rm.p[k - kb]);
-        st.t = st.p / ge.nscan;
-        st.q = decode_xy(uni_f(rm.py[k - kb]), uni_f(rm.px[k - kb]), ge);
-        return st;
-    };
-    auto tile_of = [&](const St& st, int k) {
-        return a.src + (size_t)(a.natural_tiles ? st.p : (k - a.k_begin)) * N * N;
-    };
+    auto decode = [&](int k) { return run_decode(rm, k, kb, ke, ge); };
+    auto tile_of = [&](const RunSt& st, int k) { return run_tile<N>(a, st.p, k); };
 
     __syncthreads();
     STAMP_DECL
-    St st = decode(kb);
+    RunSt st = decode(kb);
     c32 v[E];
     if (st.have && st.q.valid) {
         const c32* tile_in = tile_of(st, kb);
@@ -404,7 +359,7 @@ __global__ __launch_bounds__(Plan<N>::T * ColCfg<N>::C, 2) void k_cols_adjreg(co
             fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
     }
     for (int k = kb; k < ke; ++k) {
-        St nx = decode(k + 1);
+        RunSt nx = decode(k + 1);
         if (!st.q.valid) {   // skipped position: nothing to add; fetch the next tile
             if (nx.have && nx.q.valid) {
                 const c32* tile_in = tile_of(nx, k + 1);
@@ -529,6 +484,7 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
     // NM > 1 (forward only): NM probe modes per launch.  The bilinear patch values of a position are
     // gathered from the window ONCE and multiplied by the NM probe strips (all in VGPRs), giving the
     // strips of NM farplanes dstm[k] (ptycho.py:330-333 calls fwd once per mode and gathers each time).
+    static_assert(MODE == M_FWD || MODE == M_ADJ_PRB, "forward operator or probe adjoint");
     static_assert(NM == 1 || (MODE == M_FWD && !SPLIT), "several probe modes: un-split forward pass only");
     if (MODE == M_FWD && a.skip && *a.skip != 0.0) return;   // uniform over the grid
     using P = Plan<N>;
@@ -537,7 +493,7 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
     constexpr int E = P::E, T = P::T, C = CW ? CW : ColCfg<N>::C, NT = T * C;
     constexpr int LAST = P::NSTEP - 1;
     constexpr int WC = C + kBucketPx, H = WinCfg<N>::H;
-    constexpr int R0 = P::radix(0), RL = P::radix(LAST), NsL = P::ns(LAST);
+    constexpr int R0 = P::radix(0);
     __shared__ c32 lds[SPLIT ? 1 : N * C];
     // window rows are addressed modulo H; row H mirrors row 0, so the tap of the row below never wraps and both rows
     // of a bilinear patch are read from one base address with immediate offsets (no address arithmetic for the second)
@@ -592,22 +548,13 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
             const int iy = j0 + m * T - ge.pad;
             if (col_ok && iy >= 0 && iy < ge.nprb) {
                 const size_t e = ((size_t)t * ge.nprb + iy) * ge.nprb + ix;
-                const c32 sacc = pr[m] * cinv;
-                if (a.det_acc) {
-                    const float sc = det_sc;
-                    atomicAdd(reinterpret_cast<unsigned long long*>(a.det_acc + 2 * e), (unsigned long long)__float2ll_rn(sacc.x * sc));
-                    atomicAdd(reinterpret_cast<unsigned long long*>(a.det_acc + 2 * e + 1), (unsigned long long)__float2ll_rn(sacc.y * sc));
-                } else {
-                    float* o = reinterpret_cast<float*>(a.dst + e);
-                    atomicAdd(o, sacc.x);
-                    atomicAdd(o + 1, sacc.y);
-                }
+                accum_c32(a.dst, a.det_acc, det_sc, e, pr[m] * cinv);
             }
         }
     };
 
-    const int kb = a.k_begin + seg * seglen;
-    const int ke = kb + seglen < a.k_end ? kb + seglen : a.k_end;
+    const RunBounds rb = run_bounds(a, seg, seglen);
+    const int kb = rb.kb, ke = rb.ke;
     __shared__ RunMeta rm;
     load_run(rm, a.order, a.scan, kb, ke, tid);
 
@@ -677,6 +624,8 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
             if (pre_slot < WC) win[H * WC + pre_slot] = val;   // mirror of row 0
         }
     };
+    // (forward path only.  Writing the two calls out at its call sites reorders the register copies at the loop edges of every
+    // forward instantiation -- same instructions, another stream -- so the wrapper stays: profiles/r11/refactor_isa.txt)
     auto prepare = [&](int k, int kend) -> St {
         St st = prepare_issue(k, kend);
         prepare_commit();
@@ -689,17 +638,11 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
         // update is issued right after the exchange barrier of k, and the tile of k+1 is
         // prefetched before the accumulation of k: two barriers per position.
         auto decode_only = [&](int k) -> St {
-            St st;
-            st.have = k < ke;
-            st.p = 0; st.t = 0; st.Xa = 0; st.q = Pos{0, 0, 0.f, 0.f, false, false};
-            if (!st.have) return st;
-            st.p = rm.p[k - kb];
-            st.t = st.p / ge.nscan;
-            st.q = decode_xy(rm.py[k - kb], rm.px[k - kb], ge);
-            return st;
+            const RunSt d = run_decode<false>(rm, k, kb, ke, ge);   // per lane, without uni_i / uni_f
+            return St{d.p, d.t, 0, d.q, d.have};
         };
         auto load_tile = [&](c32* v, const St& st, int k) {
-            const c32* tile_in = a.src + (size_t)(a.natural_tiles ? st.p : (k - a.k_begin)) * N * N;
+            const c32* tile_in = run_tile<N>(a, st.p, k);
             fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
         };
         __syncthreads();   // run metadata visible
@@ -764,139 +707,126 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
             st = nx;
         }
         if (cur_t >= 0) flush_probe(cur_t);
-        return;
-    }
-    St st = prepare(kb, ke);
-    __syncthreads();
-    STAMP_DECL
-    for (int k = kb; k < ke; ++k) {
-        if (MODE == M_FWD && (NM > 1 || st.t != cur_t)) {
-            probe_strip(pr, 0, st.t);
-            cur_t = st.t;
-        }
-        if (MODE == M_ADJ_PRB && st.q.valid && st.t != cur_t) {
-            if (cur_t >= 0) flush_probe(cur_t);
-#pragma unroll
-            for (int m = 0; m < E; ++m) pr[m] = zero;
-            cur_t = st.t;
-        }
-        if (!st.q.valid) {
-            if (MODE == M_FWD) {   // skipped position: exact zeros (memset of ptychofft.cu:69)
+    } else {
+        St st = prepare(kb, ke);
+        __syncthreads();
+        STAMP_DECL
+        for (int k = kb; k < ke; ++k) {
+            if (NM > 1 || st.t != cur_t) {
+                probe_strip(pr, 0, st.t);
+                cur_t = st.t;
+            }
+            if (!st.q.valid) {   // skipped position: exact zeros (memset of ptychofft.cu:69)
 #pragma unroll
                 for (int km = 0; km < NM; ++km) {
                     c32* tile_out = (NM == 1 ? a.dst : a.dstm[km]) + (size_t)st.p * N * N;
 #pragma unroll
                     for (int m = 0; m < E; ++m) tile_out[(size_t)(j0 + m * T) * N + x] = zero;
                 }
+                __syncthreads();
+                st = prepare(k + 1, ke);
+                __syncthreads();
+                continue;
             }
-            __syncthreads();
-            st = prepare(k + 1, ke);
-            __syncthreads();
-            continue;
-        }
-        const Pos q = st.q;
-        const float w00 = (1.0f - q.fx) * (1.0f - q.fy), w01 = q.fx * (1.0f - q.fy);
-        const float w10 = (1.0f - q.fx) * q.fy, w11 = q.fx * q.fy;
-        // bilinear patch value of natural element m (row iy = j0 + m*T - pad); rows advance by T
-        // in the window, modulo H, without a division per element.  Padding rows read stale but
-        // finite window rows and are masked by the zero probe value / the select below.
-        const int colw = st.Xa - X0 + c;
-        int slot0 = (q.sy + j0 - ge.pad + 2 * H) % H;
-        auto patch_at = [&](int slot) {
-            const c32* r0 = win + slot * WC + colw;
-            return r0[0] * w00 + r0[1] * w01 + r0[WC] * w10 + r0[WC + 1] * w11;   // kernels.cu:97-104 (row H mirrors row 0)
-        };
+            const Pos q = st.q;
+            const float w00 = (1.0f - q.fx) * (1.0f - q.fy), w01 = q.fx * (1.0f - q.fy);
+            const float w10 = (1.0f - q.fx) * q.fy, w11 = q.fx * q.fy;
+            // bilinear patch value of natural element m (row iy = j0 + m*T - pad); rows advance by T
+            // in the window, modulo H, without a division per element.  Padding rows read stale but
+            // finite window rows and are masked by the zero probe value.
+            const int colw = st.Xa - X0 + c;
+            const int slot0 = (q.sy + j0 - ge.pad + 2 * H) % H;
+            auto patch_at = [&](int slot) {
+                const c32* r0 = win + slot * WC + colw;
+                return r0[0] * w00 + r0[1] * w01 + r0[WC] * w10 + r0[WC + 1] * w11;   // kernels.cu:97-104 (row H mirrors row 0)
+            };
 
-        c32 v[E];
-        c32 vbase[NM > 1 ? E : 1];   // patch values in step-0 slot order, shared by the NM modes
-        St nx;
-        if (MODE == M_FWD) {
-            STAMP(0)      // loop head
-            c32 nat[E];
-            int slot = slot0;
+            c32 v[E];
+            c32 vbase[NM > 1 ? E : 1];   // patch values in step-0 slot order, shared by the NM modes
+            St nx;
+            {   // gather (the scope ends the life of nat, the patch values in natural order)
+                STAMP(0)      // loop head
+                c32 nat[E];
+                int slot = slot0;
 #pragma unroll
-            for (int m = 0; m < E; ++m) {
-                nat[m] = patch_at(slot);
-                slot += T;
-                slot = slot >= H ? slot - H : slot;
-            }
-            F::from_natural(nat, v);
+                for (int m = 0; m < E; ++m) {
+                    nat[m] = patch_at(slot);
+                    slot += T;
+                    slot = slot >= H ? slot - H : slot;
+                }
+                F::from_natural(nat, v);
 #ifdef PTY_STAMPS
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-            for (int s2 = 0; s2 < E; ++s2) asm volatile("" : "+v"(v[s2]));
+                for (int s2 = 0; s2 < E; ++s2) asm volatile("" : "+v"(v[s2]));
 #endif
-            STAMP(1)      // gather: LDS taps + bilinear weights
-            // (Round 3 tried requesting the rows that slide in for position k + 1 HERE, ahead of this position's 16 stores
-            // -- vector memory operations complete in issue order, so the load behind the stores waits for them to drain
-            // -- : the phase stamps moved as expected, the kernel got 6 % slower (0.465 -> 0.495 ms: 112 instead of 68
-            // VGPRs and a worse schedule); profiles/r03/stamps.txt.)
-            if (NM > 1) {
+                STAMP(1)      // gather: LDS taps + bilinear weights
+                // (Round 3 tried requesting the rows that slide in for position k + 1 HERE, ahead of this position's 16 stores
+                // -- vector memory operations complete in issue order, so the load behind the stores waits for them to drain
+                // -- : the phase stamps moved as expected, the kernel got 6 % slower (0.465 -> 0.495 ms: 112 instead of 68
+                // VGPRs and a worse schedule); profiles/r03/stamps.txt.)
+                if (NM > 1) {
 #pragma unroll
-                for (int s2 = 0; s2 < E; ++s2) vbase[s2] = v[s2];
+                    for (int s2 = 0; s2 < E; ++s2) vbase[s2] = v[s2];
+                }
+#pragma unroll
+                for (int s2 = 0; s2 < E; ++s2) v[s2] = cmul(pr[s2], v[s2]);
             }
-#pragma unroll
-            for (int s2 = 0; s2 < E; ++s2) v[s2] = cmul(pr[s2], v[s2]);
-        } else {
-            const c32* tile_in = a.src + (size_t)(a.natural_tiles ? st.p : (k - a.k_begin)) * N * N;
-            fft.template load<0>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
-        }
-        fft.template compute<0>(v);
-        if (SPLIT && MODE == M_FWD) {
-            // the radix-16 outputs go straight to rows 16 j0 + k1 of the strip (Stockham step 0)
-            c32* tile_out = a.dst + (size_t)st.p * N * N;
+            fft.template compute<0>(v);
+            if (SPLIT) {
+                // the radix-16 outputs go straight to rows 16 j0 + k1 of the strip (Stockham step 0)
+                c32* tile_out = a.dst + (size_t)st.p * N * N;
 #ifdef PTY_STAMPS
 #pragma unroll
-            for (int s2 = 0; s2 < E; ++s2) asm volatile("" : "+v"(v[s2]));
+                for (int s2 = 0; s2 < E; ++s2) asm volatile("" : "+v"(v[s2]));
 #endif
-            STAMP(2)      // probe product + radix-16 step
-            fft.template store<0>(v, j0, [&](int i, c32 val) { tile_out[(size_t)i * N + x] = val; });
-            STAMP(3)      // store issue
-            __syncthreads();   // every bilinear read of position k is done
-            STAMP(4)      // barrier
-            nx = prepare_issue(k + 1, ke);
-            prepare_commit();
-            STAMP(5)      // window update (global load of the rows that slide in + LDS store)
-            __syncthreads();
-            STAMP(6)      // barrier
-            st = nx;
-            continue;
-        }
-        int jz = j0;
-        if (NM > 1) asm volatile("" : "+v"(jz));   // opaque copy: keeps the twiddle reads inside the position loop
-#pragma unroll
-        for (int km = 0; km < NM; ++km) {
-            if (NM > 1) {
-                if (km > 0) {   // next probe mode on the same patch values
-#pragma unroll
-                    for (int s2 = 0; s2 < E; ++s2) v[s2] = cmul(prnext[s2], vbase[s2]);
-                    fft.template compute<0>(v);
-                }
-                if (km + 1 < NM) probe_strip(prnext, km + 1, st.t);   // in flight during this mode's exchange steps
-            }
-            if (P::NSTEP > 1) {
-                if (MODE == M_FWD) { STAMP(2) }      // un-split forward: probe product + step 0 (+ next probe strip requested)
-                fft.template store<0>(v, j0, [&](int i, c32 val) { lds[i * C + c] = val; });
-                if (MODE == M_FWD) { STAMP(3) }      // exchange store
-                __syncthreads();
-                if (MODE == M_FWD) { STAMP(4) }      // barrier A
-                if (MODE == M_FWD && km == 0) nx = prepare_issue(k + 1, ke);   // window of k is no longer read
-                fft.template load<1>(v, j0, [&](int i) { return lds[i * C + c]; });
-                if (P::NSTEP > 2) {
-                    __syncthreads();
-                    if constexpr (NM > 1 && P::NSTEP > 2) fft.template init_step<1>(jz, wtab);
-                    fft.template compute<1>(v);
-                    fft.template store<1>(v, j0, [&](int i, c32 val) { lds[i * C + c] = val; });
-                    __syncthreads();
-                    fft.template load<2>(v, j0, [&](int i) { return lds[i * C + c]; });
-                }
-                if constexpr (NM > 1 && P::NSTEP > 1) fft.template init_step<LAST>(jz, wtab);
-                fft.template compute<LAST>(v);
-            } else if (MODE == M_FWD && km == 0) {
-                __syncthreads();
+                STAMP(2)      // probe product + radix-16 step
+                fft.template store<0>(v, j0, [&](int i, c32 val) { tile_out[(size_t)i * N + x] = val; });
+                STAMP(3)      // store issue
+                __syncthreads();   // every bilinear read of position k is done
+                STAMP(4)      // barrier
                 nx = prepare_issue(k + 1, ke);
+                prepare_commit();
+                STAMP(5)      // window update (global load of the rows that slide in + LDS store)
+                __syncthreads();
+                STAMP(6)      // barrier
+                st = nx;
+                continue;
             }
-            if (MODE == M_FWD) {
+            int jz = j0;
+            if (NM > 1) asm volatile("" : "+v"(jz));   // opaque copy: keeps the twiddle reads inside the position loop
+#pragma unroll
+            for (int km = 0; km < NM; ++km) {
+                if (NM > 1) {
+                    if (km > 0) {   // next probe mode on the same patch values
+#pragma unroll
+                        for (int s2 = 0; s2 < E; ++s2) v[s2] = cmul(prnext[s2], vbase[s2]);
+                        fft.template compute<0>(v);
+                    }
+                    if (km + 1 < NM) probe_strip(prnext, km + 1, st.t);   // in flight during this mode's exchange steps
+                }
+                if (P::NSTEP > 1) {
+                    STAMP(2)      // un-split forward: probe product + step 0 (+ next probe strip requested)
+                    fft.template store<0>(v, j0, [&](int i, c32 val) { lds[i * C + c] = val; });
+                    STAMP(3)      // exchange store
+                    __syncthreads();
+                    STAMP(4)      // barrier A
+                    if (km == 0) nx = prepare_issue(k + 1, ke);   // window of k is no longer read
+                    fft.template load<1>(v, j0, [&](int i) { return lds[i * C + c]; });
+                    if (P::NSTEP > 2) {
+                        __syncthreads();
+                        if constexpr (NM > 1 && P::NSTEP > 2) fft.template init_step<1>(jz, wtab);
+                        fft.template compute<1>(v);
+                        fft.template store<1>(v, j0, [&](int i, c32 val) { lds[i * C + c] = val; });
+                        __syncthreads();
+                        fft.template load<2>(v, j0, [&](int i) { return lds[i * C + c]; });
+                    }
+                    if constexpr (NM > 1 && P::NSTEP > 1) fft.template init_step<LAST>(jz, wtab);
+                    fft.template compute<LAST>(v);
+                } else if (km == 0) {
+                    __syncthreads();
+                    nx = prepare_issue(k + 1, ke);
+                }
                 STAMP(5)      // window request + exchange load + twiddles + last step
                 c32* tile_out = (NM == 1 ? a.dst : a.dstm[km]) + (size_t)st.p * N * N;
                 if (a.nt & 4)
@@ -908,28 +838,10 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
                 __syncthreads();   // exchange buffer / new window rows visible to everyone
                 STAMP(7)      // window commit + barrier B
             }
+            st = nx;
         }
-        if (MODE != M_FWD) {
-            c32 nat[E];
-            F::to_natural(v, nat);
-            int slot = slot0;
-#pragma unroll
-            for (int m = 0; m < E; ++m) {
-                const int iy = j0 + m * T - ge.pad;
-                const bool ok = col_ok && iy >= 0 && iy < ge.nprb;
-                const c32 term = cmulc(nat[m], patch_at(slot));
-                pr[m] += ok ? term : zero;
-                slot += T;
-                slot = slot >= H ? slot - H : slot;
-            }
-            __syncthreads();   // everyone is done with the window of k and the exchange buffer
-            nx = prepare(k + 1, ke);
-            __syncthreads();
-        }
-        st = nx;
+        STAMP_FLUSH(a.stamps)
     }
-    if (MODE == M_ADJ_PRB && cur_t >= 0) flush_probe(cur_t);
-    if (MODE == M_FWD) { STAMP_FLUSH(a.stamps) }
 }
 
 // ---------------------------------------------------------------------------

@@ -155,15 +155,7 @@ __global__ void k_adj_prb_generic(const c32* __restrict__ f, c32* __restrict__ p
     if (pix >= ge.nprb * ge.nprb) return;
     const float det_sc = det_acc ? det_scale_of(det) : 0.0f;
     auto add = [&](int t, int iy, int ix, c32 v) {   // one group's share of prb[t][iy][ix]
-        const size_t e = ((size_t)t * ge.nprb + iy) * ge.nprb + ix;
-        if (det_acc) {
-            atomicAdd(reinterpret_cast<unsigned long long*>(det_acc + 2 * e), (unsigned long long)__float2ll_rn(v.x * det_sc));
-            atomicAdd(reinterpret_cast<unsigned long long*>(det_acc + 2 * e + 1), (unsigned long long)__float2ll_rn(v.y * det_sc));
-        } else {
-            float* o = reinterpret_cast<float*>(prb + e);
-            atomicAdd(o, v.x);
-            atomicAdd(o + 1, v.y);
-        }
+        accum_c32(prb, det_acc, det_sc, ((size_t)t * ge.nprb + iy) * ge.nprb + ix, v);
     };
     const int ix = pix % ge.nprb, iy = pix / ge.nprb;
     const int N = ge.ndet;
@@ -220,29 +212,22 @@ __global__ __launch_bounds__(256) void k_adjwin_generic(const ColArgs a, const i
             const int X = X0 + col;
             if ((v.x != 0.0f || v.y != 0.0f) && Y < ge.nz && X >= 0 && X < ge.n) {
                 const size_t e = ((size_t)t_w * ge.nz + Y) * ge.n + X;
-                if (a.det_acc) {   // integer atomics: the sum does not depend on the arrival order
-                    atomicAdd(reinterpret_cast<unsigned long long*>(a.det_acc + 2 * e), (unsigned long long)__float2ll_rn(v.x * det_sc));
-                    atomicAdd(reinterpret_cast<unsigned long long*>(a.det_acc + 2 * e + 1), (unsigned long long)__float2ll_rn(v.y * det_sc));
-                } else {
-                    float* op = reinterpret_cast<float*>(a.dst + e);
-                    atomicAdd(op, v.x);
-                    atomicAdd(op + 1, v.y);
-                }
+                accum_c32(a.dst, a.det_acc, det_sc, e, v);
             }
         }
     };
     constexpr int NRG = NT / (C + 1), NITEM = (C + 1) * NRG;
     const int rpt = (ge.nprb + 1 + NRG - 1) / NRG;  // output rows per item
 
-    const int kb = a.k_begin + seg * seglen;
-    const int ke = kb + seglen < a.k_end ? kb + seglen : a.k_end;
+    const RunBounds rb = run_bounds(a, seg, seglen);
+    const int kb = rb.kb, ke = rb.ke;
     __shared__ RunMeta rm;
     load_run(rm, a.order, a.scan, kb, ke, tid);
     __syncthreads();
     for (int k = kb; k < ke; ++k) {
-        const int p = uni_i(rm.p[k - kb]);
-        const int t = p / ge.nscan;
-        const Pos q = decode_xy(uni_f(rm.py[k - kb]), uni_f(rm.px[k - kb]), ge);
+        const RunSt st = run_decode(rm, k, kb, ke, ge);
+        const int t = st.t;
+        const Pos q = st.q;
         if (!q.valid) continue;                     // uniform
         const c32* __restrict__ near = a.src + (size_t)(k - a.k_begin) * N * N;
         const c32* __restrict__ prb = a.aux + (size_t)t * ge.nprb * ge.nprb;

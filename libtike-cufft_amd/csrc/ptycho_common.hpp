@@ -1,4 +1,4 @@
-// ptycho_common.hpp -- geometry, kernel argument structs, position decoding, run metadata
+// ptycho_common.hpp -- geometry, kernel argument structs, position decoding, run metadata and decode, accumulate
 // Part of libptychohip (see ptycho_kernels.hip); included inside its anonymous namespace.
 #pragma once
 
@@ -132,7 +132,8 @@ __device__ __forceinline__ float uni_f(float v) { return __int_as_float(__builti
 
 // positions of one run (<= kRunMax), staged in LDS once per workgroup so that the per-position
 // loop has no dependent global loads (order[k] -> scan[p]) on its critical path
-constexpr int kRunMax = 128;
+// (kRunMax: run_split.hpp, namespace pty.  This file is included INSIDE the anonymous namespace of ptycho_kernels.hip, so it
+// cannot include that header itself; ptycho_kernels.hip includes it first, as it does fft_core.hpp and adjreg_map.hpp.)
 struct RunMeta {
     int p[kRunMax];
     float py[kRunMax], px[kRunMax];
@@ -145,6 +146,49 @@ __device__ __forceinline__ void load_run(RunMeta& rm, const int* __restrict__ or
         rm.p[i] = p;
         rm.py[i] = scan[2 * (size_t)p];
         rm.px[i] = scan[2 * (size_t)p + 1];
+    }
+}
+
+// ---- the pieces the run-structured column kernels share (k_cols_window.hpp, k_adjwin_generic) ------------------------------
+// positions [kb, ke) of run seg of a launch cut into runs of seglen (host: split_runs, run_split.hpp)
+struct RunBounds { int kb, ke; };
+__device__ __forceinline__ RunBounds run_bounds(const ColArgs& a, int seg, int seglen) {
+    const int kb = a.k_begin + seg * seglen;
+    return RunBounds{kb, kb + seglen < a.k_end ? kb + seglen : a.k_end};
+}
+// k-th sorted position from the staged run: index, angle, decoded coordinates; have = false past the end of the run.
+// UNI: the values are the same in every lane and go to scalar registers (uni_i / uni_f); the probe-adjoint loop of
+// k_cols_gatherwin reads them as they are.
+struct RunSt { int p, t; Pos q; bool have; };
+template <bool UNI = true>
+__device__ __forceinline__ RunSt run_decode(const RunMeta& rm, int k, int kb, int ke, const Geom& ge) {
+    RunSt st;
+    st.have = k < ke;
+    st.p = 0; st.t = 0; st.q = Pos{0, 0, 0.f, 0.f, false, false};
+    if (!st.have) return st;
+    st.p = UNI ? uni_i(rm.p[k - kb]) : rm.p[k - kb];
+    st.t = st.p / ge.nscan;
+    st.q = UNI ? decode_xy(uni_f(rm.py[k - kb]), uni_f(rm.px[k - kb]), ge) : decode_xy(rm.py[k - kb], rm.px[k - kb], ge);
+    return st;
+}
+// tile of the k-th sorted position (index p) of an adjoint launch: ColArgs::natural_tiles
+// (object-space bands -- a workgroup owns 16 OBJECT columns -- would read row pieces that straddle two 128-byte lines and
+// reload the probe strip for every position: both priced and refuted, profiles/r04/adjwin_ablations.txt)
+template <int N>
+__device__ __forceinline__ const c32* run_tile(const ColArgs& a, int p, int k) {
+    return a.src + (size_t)(a.natural_tiles ? p : (k - a.k_begin)) * N * N;
+}
+
+// dst[e] += v: two float atomics, or -- deterministic option -- integer atomics on the 64-bit fixed-point image det_acc
+// (associative, so the sum does not depend on the arrival order); det_sc = det_scale_of(ColArgs::det)
+__device__ __forceinline__ void accum_c32(c32* dst, long long* det_acc, float det_sc, size_t e, c32 v) {
+    if (det_acc) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(det_acc + 2 * e), (unsigned long long)__float2ll_rn(v.x * det_sc));
+        atomicAdd(reinterpret_cast<unsigned long long*>(det_acc + 2 * e + 1), (unsigned long long)__float2ll_rn(v.y * det_sc));
+    } else {
+        float* o = reinterpret_cast<float*>(dst + e);
+        atomicAdd(o, v.x);
+        atomicAdd(o + 1, v.y);
     }
 }
 

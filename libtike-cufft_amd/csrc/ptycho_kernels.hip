@@ -21,7 +21,9 @@
 // The adjoint's intermediate lives in a scratch of at most 4 GiB (one launch pair per chunk of positions; at
 // 4096 x 256^2 that is a single pair).
 //
-// Reading order: kernel headers (k_*.hpp), then the host side by topic -- host_handle.hpp (handle, errors, profiler,
+// Reading order: ptycho_common.hpp first (arguments, and what the run-structured column kernels share: run bounds and
+// decode, tile address, accumulate; run_split.hpp is the host's half of the run structure), then the kernel headers (k_*.hpp), then
+// the host side by topic -- host_handle.hpp (handle, errors, profiler,
 // allocations, dispatch macros), host_ops.hpp (launchers and the three operators), host_cg.hpp (CG stages) -- and
 // below them nothing but the exported functions: argument checks in the order the tests rely on, then one call.
 #include <hip/hip_runtime.h>
@@ -36,6 +38,7 @@
 
 #include "../../include/ptycho_hip.h"
 #include "fft_core.hpp"
+#include "run_split.hpp"
 #include "adjreg_map.hpp"
 #include "k_modes.hpp"
 #include "k_frc.hpp"

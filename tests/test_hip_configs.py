@@ -4,7 +4,7 @@ BASELINE.json configs, and what checks each of them here:
 
 * configs[1]  4096 x 256^2, 1 mode, 50 CG iterations
     - ``test_cg256_tracks_the_oracle``: the fused N = 256 kernels (16 x 16 plan, unsplit
-      column passes, ``k_rows_fused<256, EP>``, ``k_cols_adjwin<256>``, ``k_cols_argmax<256>``,
+      column passes, ``k_rows_fused<256, EP>``, ``k_cols_adjreg<256>``, ``k_cols_argmax<256>``,
       ``k_zoom_mfma<256>``) against ``oracle.cg_oracle`` on the configs[1] geometry cut to
       8 x 8 positions: identical step sizes, cost within 1e-4, psi / probe within 2e-4;
     - ``test_cg_full_size_properties``: the full 4096 x 256^2 problem: 50 iterations with a

@@ -120,6 +120,19 @@ def test_fft_core_on_host(tmp_path):
     assert "OK" in out.stdout.splitlines()[-1]
 
 
+def test_run_split_on_host(tmp_path):
+    """csrc/run_split.hpp, the split of a windowed column launch into runs, swept over 1 .. 5000 positions, 1 .. 32
+    strips, 1 .. 304 CUs and the launchers' workgroup targets: every run fits RunMeta (<= kRunMax positions, the only
+    guard of load_run), the runs cover the positions, none is empty, and the result is the formula the four launch
+    sites used to write out."""
+    exe = str(tmp_path / "pty_host_runsplit")
+    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2", "-Wall",
+                    os.path.join(CSRC, "host_runsplit.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout
+    assert out.stdout.splitlines()[-1] == "host_runsplit: 360000 cases, longest run 128 of 128, 0 errors", out.stdout
+
+
 def test_python_api_mirrors_reference_names():
     import libtike.hipfft as pt
     import libtike.cufft as alias
