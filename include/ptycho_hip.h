@@ -230,6 +230,47 @@ int ptycho_prepare_frames(float* data, unsigned char* mask, double* frames, doub
                           size_t ptheta, size_t nraw, size_t nscan, size_t H, size_t W, long long y0, long long x0,
                           int bin, size_t ndet, float saturation, float scale, int clip, double* work, void* stream);
 
+/* Weighted least-squares phase unwrapping (no handle; libtike.hipfft.unwrap): Jacobi-preconditioned conjugate gradients
+ * on the pixel grid (Ghiglia & Romero 1994).  Every launch runs on `stream`, nothing synchronises, no float atomics and
+ * fixed summation orders: the same inputs give the same bits.  ptheta in [1, 65535], nz >= 2, n >= 2, nz * n < 2^31.
+ * Per angle: phase phi and weight w are float32 [nz][n] (weight NULL: all ones).  w' = w where w > 0 and finite, else 0 (a
+ * select).  W(a) = a - 2 pi rint(a / 2 pi) in float32.  The edge between neighbours p -> q (q to the right of or below
+ * p) has weight w_e = min(w'_p, w'_q) and difference d_e = W(phi_q - phi_p); an edge of weight 0 contributes exactly 0 to
+ * everything, whatever phi holds at its ends.  The solver minimises sum_e w_e (x_q - x_p - d_e)^2, i.e. L x = b with
+ * (L x)_p = sum_{e at p} w_e (x_p - x_other), b_p = sum_{e into p} w_e d_e - sum_{e out of p} w_e d_e, D_p = sum_{e at p}
+ * w_e and the preconditioner 1 / D (0 where D = 0), from x = 0.  Arrays are float32; every dot product, alpha, beta and the
+ * stopping tests are float64.
+ *   state   float64 [ptheta][PTYCHO_UNWRAP_STATE_WORDS]: rz0, rz, p.q, alpha, beta, iterations, status (0 running,
+ *           1 converged: rz <= tol^2 rz0, rz0 = 0 included; 2 breakdown: p.q <= 0 or not finite, x stays as it is;
+ *           3 maxiter), relres = sqrt(rz / rz0), c; the rest is zero.
+ *   buf     float32 scratch of ptycho_unwrap_buffer_floats words: per angle the planes x, r, p, p', q, 1 / D.
+ *   work    float64 scratch of ptycho_unwrap_work_words words (both 0 for sizes out of range).
+ *   ptycho_unwrap_begin     b -> r, 1 / D, x = 0, p = r / D, rz0; state is initialised.  Two launches.
+ *   ptycho_unwrap_iterate   enqueues niter iterations (q = L p, alpha = rz / p.q, x += alpha p, r -= alpha q, z = r / D,
+ *                           rz' = r.z, p = z + (rz' / rz) p), four launches each, and one more that applies the stopping
+ *                           tests; the launches of an angle that has stopped return at once, and no angle runs past
+ *                           maxiter however many iterations are enqueued.  weight: as given to begin.
+ *   ptycho_unwrap_finish    c = arg sum w' [D > 0] exp(i (phi - x)) (arg 0 = 0) -> state; congruent != 0:
+ *                           out = phi + 2 pi rint((x + c - phi) / 2 pi), formed in float64 and rounded once;
+ *                           congruent = 0: out = x + c; out = phi where D = 0.  Three launches.
+ *   ptycho_unwrap_residues  charge (int8 [ptheta][nz-1][n-1], or NULL) <- for the loop with corner (y, x),
+ *                           rint((W(phi[y][x+1] - phi[y][x]) + W(phi[y+1][x+1] - phi[y][x+1]) + W(phi[y+1][x] -
+ *                           phi[y+1][x+1]) + W(phi[y][x] - phi[y+1][x])) / 2 pi) if all four pixels have w' > 0, else 0;
+ *                           count (int64 [ptheta]) <- the number of loops of charge +-1.  A memset and one launch.
+ * PTYCHO_ERR_ARG, before any HIP call, for a null buf / state / phase / work / out / count, nz < 2 or n < 2,
+ * nz * n >= 2^31, ptheta outside [1, 65535], niter < 0, maxiter < 0, or a tol that is negative or not finite. */
+#define PTYCHO_UNWRAP_STATE_WORDS 16
+size_t ptycho_unwrap_work_words(size_t ptheta, size_t nz, size_t n);
+size_t ptycho_unwrap_buffer_floats(size_t ptheta, size_t nz, size_t n);
+int ptycho_unwrap_begin(float* buf, double* state, const float* phase, const float* weight, size_t ptheta, size_t nz,
+                        size_t n, double* work, void* stream);
+int ptycho_unwrap_iterate(float* buf, double* state, const float* weight, size_t ptheta, size_t nz, size_t n, int niter,
+                          int maxiter, double tol, double* work, void* stream);
+int ptycho_unwrap_finish(float* out, double* state, const float* buf, const float* phase, const float* weight,
+                         int congruent, size_t ptheta, size_t nz, size_t n, double* work, void* stream);
+int ptycho_unwrap_residues(signed char* charge, long long* count, const float* phase, const float* weight, size_t ptheta,
+                           size_t nz, size_t n, void* stream);
+
 /* ---- fused CG-stage entry points ("plus fused CG-stage entry points") ----
  * The elementwise stages of CGPtychoSolver.run (src/libtike/cufft/ptycho.py:325-393) are
  * fused into the row pass of the DFT so that farplanes are never materialised.  The

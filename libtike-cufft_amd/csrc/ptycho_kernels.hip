@@ -45,6 +45,7 @@
 #include "k_gauge.hpp"
 #include "k_fit.hpp"
 #include "k_prepare.hpp"
+#include "k_unwrap.hpp"
 
 using namespace pty;
 
@@ -68,6 +69,7 @@ namespace {
 #include "host_gauge.hpp"
 #include "host_fit.hpp"
 #include "host_prepare.hpp"
+#include "host_unwrap.hpp"
 
 extern "C" {
 
@@ -812,6 +814,57 @@ int ptycho_prepare_frames(float* data, unsigned char* mask, double* frames, doub
     const PrepGeom g{(long long)H, (long long)W, y0, x0, bin, (int)ndet};
     return do_prepare_frames(data, mask, frames, pixels, raw, dtype, index, dark, gain, bad, (long long)ptheta,
                              (long long)nraw, (long long)nscan, g, saturation, scale, clip, work, (hipStream_t)stream);
+}
+
+// ---- weighted least-squares phase unwrapping (k_unwrap.hpp, libtike.hipfft.unwrap): no handle ----------------------------
+size_t ptycho_unwrap_work_words(size_t ptheta, size_t nz, size_t n) {
+    if (!unwrap_sizes_ok(ptheta, nz, n)) return 0;
+    return ptheta * (size_t)unwrap_tiles((int)nz, (int)n) * kUnwPart;
+}
+
+size_t ptycho_unwrap_buffer_floats(size_t ptheta, size_t nz, size_t n) {
+    if (!unwrap_sizes_ok(ptheta, nz, n)) return 0;
+    return ptheta * kUnwPlanes * nz * n;
+}
+
+static int unwrap_check_sizes(size_t ptheta, size_t nz, size_t n) {
+    if (ptheta == 0 || ptheta > kUnwMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
+    if (nz < 2 || n < 2) return fail(PTYCHO_ERR_ARG, "nz and n must be at least 2");
+    if (!unwrap_sizes_ok(ptheta, nz, n)) return fail(PTYCHO_ERR_ARG, "nz * n too large: it must stay below 2^31");
+    return PTYCHO_OK;
+}
+
+int ptycho_unwrap_begin(float* buf, double* state, const float* phase, const float* weight, size_t ptheta, size_t nz,
+                        size_t n, double* work, void* stream) {
+    if (!buf || !state || !phase || !work) return fail(PTYCHO_ERR_ARG, "buf, state, phase and work must not be null");
+    if (int rc = unwrap_check_sizes(ptheta, nz, n)) return rc;
+    return do_unwrap_begin(buf, state, phase, weight, (int)ptheta, (int)nz, (int)n, work, (hipStream_t)stream);
+}
+
+int ptycho_unwrap_iterate(float* buf, double* state, const float* weight, size_t ptheta, size_t nz, size_t n, int niter,
+                          int maxiter, double tol, double* work, void* stream) {
+    if (!buf || !state || !work) return fail(PTYCHO_ERR_ARG, "buf, state and work must not be null");
+    if (int rc = unwrap_check_sizes(ptheta, nz, n)) return rc;
+    if (niter < 0 || maxiter < 0) return fail(PTYCHO_ERR_ARG, "niter and maxiter must not be negative");
+    if (!(tol >= 0.0) || !(tol < INFINITY)) return fail(PTYCHO_ERR_ARG, "tol must be finite and not negative");
+    return do_unwrap_iterate(buf, state, weight, (int)ptheta, (int)nz, (int)n, niter, maxiter, tol, work,
+                             (hipStream_t)stream);
+}
+
+int ptycho_unwrap_finish(float* out, double* state, const float* buf, const float* phase, const float* weight,
+                         int congruent, size_t ptheta, size_t nz, size_t n, double* work, void* stream) {
+    if (!out || !state || !buf || !phase || !work)
+        return fail(PTYCHO_ERR_ARG, "out, state, buf, phase and work must not be null");
+    if (int rc = unwrap_check_sizes(ptheta, nz, n)) return rc;
+    return do_unwrap_finish(out, state, buf, phase, weight, congruent != 0, (int)ptheta, (int)nz, (int)n, work,
+                            (hipStream_t)stream);
+}
+
+int ptycho_unwrap_residues(signed char* charge, long long* count, const float* phase, const float* weight, size_t ptheta,
+                           size_t nz, size_t n, void* stream) {
+    if (!count || !phase) return fail(PTYCHO_ERR_ARG, "count and phase must not be null");
+    if (int rc = unwrap_check_sizes(ptheta, nz, n)) return rc;
+    return do_unwrap_residues(charge, count, phase, weight, (int)ptheta, (int)nz, (int)n, (hipStream_t)stream);
 }
 
 }  // extern "C"

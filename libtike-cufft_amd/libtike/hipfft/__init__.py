@@ -5,5 +5,6 @@ from libtike.hipfft.frc import frc  # noqa: F401
 from libtike.hipfft.gauge import illumination, fit_gauge, apply_gauge, fix_gauge  # noqa: F401
 from libtike.hipfft.fit import fit_frames, accumulate_intensity, flag_frames  # noqa: F401
 from libtike.hipfft.prepare import prepare_frames, initial_probe  # noqa: F401
+from libtike.hipfft.unwrap import unwrap_phase, phase_residues  # noqa: F401
 
 __version__ = "0.1.0"

@@ -31,6 +31,8 @@ SYMBOLS = ("ptycho_create", "ptycho_free", "ptycho_destroy", "ptycho_get",
            "ptycho_illumination", "ptycho_gauge_fit", "ptycho_gauge_apply",
            "ptycho_fit_accumulate", "ptycho_fit_work_words", "ptycho_fit_frames",
            "ptycho_prepare_work_words", "ptycho_prepare_frames",
+           "ptycho_unwrap_work_words", "ptycho_unwrap_buffer_floats", "ptycho_unwrap_begin", "ptycho_unwrap_iterate",
+           "ptycho_unwrap_finish", "ptycho_unwrap_residues",
            "ptycho_last_error", "ptycho_version")
 
 if not os.path.exists(LIB_PATH):
@@ -119,6 +121,20 @@ prepare_frames = _sig("ptycho_prepare_frames", _i, _vp, _vp, _vp, _vp, _vp, _i, 
                       _ll, _ll, _i, _sz, ctypes.c_float, ctypes.c_float, _i, _vp, _vp)
 #: ``dtype`` codes of ``prepare_frames``'s raw frames
 PREPARE_DTYPES = {"uint16": 0, "uint32": 1, "int32": 2, "float32": 3}
+#: phase unwrapping (no handle): ptheta, nz, n -> float64 words of scratch / float32 words of ``buf`` (0: out of range)
+unwrap_work_words = _sig("ptycho_unwrap_work_words", _sz, _sz, _sz, _sz)
+unwrap_buffer_floats = _sig("ptycho_unwrap_buffer_floats", _sz, _sz, _sz, _sz)
+#: buf, state, phase, weight, ptheta, nz, n, work, stream
+unwrap_begin = _sig("ptycho_unwrap_begin", _i, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp)
+#: buf, state, weight, ptheta, nz, n, niter, maxiter, tol, work, stream
+unwrap_iterate = _sig("ptycho_unwrap_iterate", _i, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, ctypes.c_double, _vp, _vp)
+#: out, state, buf, phase, weight, congruent, ptheta, nz, n, work, stream
+unwrap_finish = _sig("ptycho_unwrap_finish", _i, _vp, _vp, _vp, _vp, _vp, _i, _sz, _sz, _sz, _vp, _vp)
+#: charge, count, phase, weight, ptheta, nz, n, stream
+unwrap_residues = _sig("ptycho_unwrap_residues", _i, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp)
+#: float64 words of the unwrapper's state per angle (PTYCHO_UNWRAP_STATE_WORDS) and the slots the wrapper reads
+UNWRAP_STATE_WORDS = 16
+UNWRAP_ITER, UNWRAP_STATUS, UNWRAP_RELRES, UNWRAP_C = 5, 6, 7, 8
 #: ``get`` keys: options "chunk" and "window" as set; ``GET_WORK_SLOT0 + s``: 1 if CG work slot ``s`` holds device memory
 GET_CHUNK, GET_WINDOW, GET_WORK_SLOT0 = 100, 101, 200
 #: ``get`` key: 1 if a measured-pixel mask is set on the handle
