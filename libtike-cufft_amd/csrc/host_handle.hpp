@@ -86,6 +86,43 @@ int fail(int code, const std::string& msg) {
             return fail(PTYCHO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// the host's half of a FramePart (frame_part.hpp) for checked sizes: the plan and the launch grid of the pass, where the
+// pass writes (fpart, ppart), and after the pass the fold of whatever it left in work (nothing: one wave tile and one range)
+template <class Part>
+struct FrameFold {
+    FramePlan p;
+    double *frames, *pixels, *fpart, *ppart;
+    long long ptheta, nscan, npix;
+    FrameFold(double* frames_, double* pixels_, double* work, long long ptheta_, long long nscan_, long long npix_)
+        : p(Part::plan(ptheta_, nscan_, npix_)), frames(frames_), pixels(pixels_), fpart(p.fwords ? work : frames_),
+          ppart(p.pwords ? work + p.fwords : pixels_), ptheta(ptheta_), nscan(nscan_), npix(npix_) {}
+    dim3 grid() const { return dim3((unsigned)p.ntiles, (unsigned)p.nranges, (unsigned)ptheta); }
+    // pix: the kernel's own eighth argument, the slab Part::kMaps * npix (k_fit_fold) or npix (k_prepare_fold)
+    template <class K>
+    int fold(K kernel, long long pix, hipStream_t st) const {
+        const long long nfout = p.fwords ? ptheta * nscan * Part::kCols : 0;
+        const long long npout = p.pwords && pixels ? ptheta * Part::kMaps * npix : 0;
+        const long long fblocks = (nfout + 255) / 256, pblocks = (npout + 255) / 256;
+        if (fblocks + pblocks > 0) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)(fblocks + pblocks)), dim3(256), 0, st, frames, pixels,
+                               (const double*)fpart, (const double*)ppart, nfout, p.nwt, npout, pix, p.nranges,
+                               (unsigned)fblocks);
+            HIP_TRY(hipGetLastError());
+        }
+        return PTYCHO_OK;
+    }
+};
+
+// body of ptycho_fit_work_words / ptycho_prepare_work_words; ok: the sizes passed the caller's limits
+template <class Part>
+size_t frame_work_words(bool ok, size_t ptheta, size_t nscan, size_t npix) {
+    if (!ok) return 0;
+    const FramePlan p = Part::plan((long long)ptheta, (long long)nscan, (long long)npix);
+    return (size_t)(p.fwords + p.pwords);
+}
+
 // prologue of an entry point: the handle is live and none of the operands is null
 template <class... P>
 int check_args(ptycho_handle h, const P*... operands) {

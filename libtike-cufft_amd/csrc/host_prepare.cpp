@@ -1,6 +1,5 @@
-// Host build of the partition of k_prepare / k_prepare_fold and of the crop / shift index map (k_prepare.hpp): workgroup
-// tiles, waves, lanes and their pixel groups, the frame ranges, the lanes that store a frame's four figures, and the words
-// of `work` that the pass writes and the fold reads, walked as the kernels walk them.  No GPU involved.
+// Host build of the partition of k_prepare / k_prepare_fold (PrepPart, walked by frame_part_walk.hpp as the kernels walk
+// it) and of the crop / shift index map (k_prepare.hpp).  No GPU involved.
 //
 //   host_prepare                              the walk and the map at a list of shapes of its own; exit status 1 on an error
 //   host_prepare walk ptheta nscan ndet       stdout "errors words nranges nwt": errors counts the (frame, pixel) pairs
@@ -11,90 +10,48 @@
 //                                             aligned": the centred pixel it holds, the offsets of the first and the last
 //                                             raw pixel of its bin in the frame (-1: outside), and whether the vector
 //                                             loads apply to this geometry
-//
-// A workgroup is (tile, range, angle) and visits {pixels of the tile} x {frames of the range}: the number of visits of a
-// pair is the product of the two factors, which the walk counts separately.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
+#include "frame_part_walk.hpp"
 #include "k_prepare.hpp"
 
 using namespace pty;
 
-static long long walk(const long long ptheta, const long long nscan, const int ndet, PrepPlan& p) {
-    const long long npix = (long long)ndet * ndet;
-    p = prep_plan(ptheta, nscan, npix);
-    const long long words = p.fwords + p.pwords;
-    long long errors = 0;
-    std::vector<unsigned char> wrote((size_t)words, 0), folded((size_t)words, 0), mask((size_t)npix, 0);
-    for (long long t = 0; t < ptheta; ++t) {
-        std::vector<unsigned> fvis((size_t)nscan, 0), pvis((size_t)npix, 0), cvis((size_t)npix, 0);
-        std::vector<unsigned char> fout((size_t)nscan * kPrepCols, 0), pout((size_t)kPrepMaps * npix, 0);
-        for (long long r = 0; r < p.nranges; ++r) {
-            const long long j0 = r * p.flen, j1 = j0 + p.flen < nscan ? j0 + p.flen : nscan;
-            if (j0 >= j1) ++errors;   // an empty range would be a workgroup with nothing to do
-            for (long long j = j0; j < j1; ++j) ++fvis[(size_t)j];
-        }
-        for (long long tile = 0; tile < p.ntiles; ++tile)
-            for (int wave = 0; wave < kPrepWaves; ++wave) {
-                const long long wt = tile * kPrepWaves + wave;
-                if (wt >= p.nwt) continue;
-                bool any = false;
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int q = 0; q < kPrepSlots; ++q) {
-                        const long long px = prep_pixel(wt, lane, q / kPrepLanePix) + q % kPrepLanePix;
-                        if (px >= npix) continue;
-                        ++pvis[(size_t)px];
-                        any = true;
-                        int oy, ox;
-                        prep_centred(px, ndet, oy, ox);
-                        if (oy < 0 || oy >= ndet || ox < 0 || ox >= ndet) ++errors;
-                        else ++cvis[(size_t)oy * ndet + ox];
-                        if (t == 0) ++mask[(size_t)px];   // range 0 of angle 0 writes the mask
-                        for (long long r = 0; r < p.nranges; ++r)
-                            for (int m = 0; m < kPrepMaps; ++m) {
-                                if (p.pwords) ++wrote[(size_t)(p.fwords + prep_pixel_word(t, r, m, p.nranges, npix) + px)];
-                                else ++pout[(size_t)m * npix + px];
-                            }
-                    }
-                if (!any) ++errors;   // a live wave tile holds at least one pixel
-                // lanes 0, 16, 32, 48 of the wave store the four figures of every frame of every range
-                for (long long r = 0; r < p.nranges; ++r)
-                    for (long long j = r * p.flen; j < (r + 1) * p.flen && j < nscan; ++j)
-                        for (int lane = 0; lane < 64; lane += 16) {
-                            const int e = prep_lane_col(lane);
-                            if (e < 0 || e >= kPrepCols) { ++errors; continue; }
-                            if (p.fwords) ++wrote[(size_t)(prep_frame_word(t * nscan + j, wt, p.nwt) + e)];
-                            else ++fout[(size_t)j * kPrepCols + e];
-                        }
-            }
-        // the fold: one thread per output word
-        if (p.fwords)
-            for (long long i = 0; i < nscan * kPrepCols; ++i) {
-                const long long frame = t * nscan + i / kPrepCols, e = i % kPrepCols;
-                for (long long w = 0; w < p.nwt; ++w) ++folded[(size_t)(prep_frame_word(frame, w, p.nwt) + e)];
-                ++fout[(size_t)i];
-            }
-        if (p.pwords) {
-            const long long slab = kPrepMaps * npix;
-            for (long long rem = 0; rem < slab; ++rem) {
-                for (long long r = 0; r < p.nranges; ++r) ++folded[(size_t)(p.fwords + (t * p.nranges + r) * slab + rem)];
-                ++pout[(size_t)rem];
-            }
-        }
-        long long f1 = 0, p1 = 0;
-        for (unsigned v : fvis) f1 += v == 1;
-        for (unsigned v : pvis) p1 += v == 1;
-        errors += nscan * npix - f1 * p1;
-        for (unsigned v : cvis) errors += v != 1;
-        for (unsigned char v : fout) errors += v != 1;
-        for (unsigned char v : pout) errors += v != 1;
+// what preparation adds to the walk: the shift hits every centred pixel once, range 0 of angle 0 writes the mask, and lanes
+// 0, 16, 32, 48 store the frame's four figures in the order of prep_lane_col
+struct PrepWalkHook : FrameWalkHook<PrepPart> {
+    static constexpr int kStoreStride = 16;
+    const int ndet;
+    long long bad = 0;
+    std::vector<unsigned> cvis;
+    std::vector<unsigned char> mask;
+    explicit PrepWalkHook(const int n) : ndet(n), cvis((size_t)n * n, 0), mask((size_t)n * n, 0) {}
+    int col(const int lane) const { return prep_lane_col(lane); }
+    void pixel(const long long t, const long long px) {
+        int oy, ox;
+        prep_centred(px, ndet, oy, ox);
+        if (oy < 0 || oy >= ndet || ox < 0 || ox >= ndet) ++bad;
+        else ++cvis[(size_t)oy * ndet + ox];
+        if (t == 0) ++mask[(size_t)px];
     }
-    for (unsigned char v : mask) errors += v != 1;
-    for (long long i = 0; i < words; ++i) errors += (wrote[(size_t)i] != 1) + (folded[(size_t)i] != 1);
-    return errors;
+    long long angle_errors() {
+        long long e = 0;
+        for (unsigned& v : cvis) { e += v != 1; v = 0; }
+        return e;
+    }
+    long long errors() const {
+        long long e = bad;
+        for (unsigned char v : mask) e += v != 1;
+        return e;
+    }
+};
+
+static long long walk(const long long ptheta, const long long nscan, const int ndet, FramePlan& p) {
+    PrepWalkHook hook(ndet);
+    return walk_frame_part<PrepPart>(ptheta, nscan, (long long)ndet * ndet, p, hook);
 }
 
 // the index map against its definition written out: data[r][c] = v[(r + ndet / 2) % ndet][(c + ndet / 2) % ndet], and a raw
@@ -115,12 +72,12 @@ static long long check_map(const PrepGeom& g) {
                 }
             // with the vector loads a run of four raw elements from the first of a lane's group is inside or outside as a
             // whole and starts on a multiple of four elements
-            if (prep_runs_aligned(g) && c % kPrepLanePix == 0)
+            if (prep_runs_aligned(g) && c % PrepPart::kLanePix == 0)
                 for (int by = 0; by < g.bin; ++by)
                     for (int u = 0; u < g.bin; ++u) {
                         const long long x = g.x0 + (long long)ox * g.bin + 4 * u;
                         errors += ((x % 4) + 4) % 4 != 0 || (x >= 0) != (x + 3 >= 0) || (x < g.W) != (x + 3 < g.W);
-                        errors += ox + kPrepLanePix > n;   // the group does not wrap
+                        errors += ox + PrepPart::kLanePix > n;   // the group does not wrap
                     }
         }
     return errors;
@@ -131,7 +88,7 @@ int main(int argc, char** argv) {
         const unsigned long long ptheta = std::strtoull(argv[2], nullptr, 10), nscan = std::strtoull(argv[3], nullptr, 10),
                                  ndet = std::strtoull(argv[4], nullptr, 10);
         if (ndet == 0 || ndet > kPrepMaxNdet || !prep_sizes_ok(ptheta, nscan, ndet * ndet)) return 2;
-        PrepPlan p;
+        FramePlan p;
         const long long errors = walk((long long)ptheta, (long long)nscan, (int)ndet, p);
         std::printf("%lld %lld %lld %lld\n", errors, p.fwords + p.pwords, p.nranges, p.nwt);
         return 0;
@@ -155,7 +112,7 @@ int main(int argc, char** argv) {
                                    {3, 129, 2}, {1, 5, 3}, {2, 1000, 33}, {1, 4096, 256}, {1, 257, 45}};
     long long errors = 0;
     for (const auto& s : shapes) {
-        PrepPlan p;
+        FramePlan p;
         const long long e = walk(s[0], s[1], (int)s[2], p);
         std::printf("walk %lld x %lld x %lld^2: %lld ranges, %lld wave tiles, %lld words, %lld errors\n", s[0], s[1], s[2],
                     p.nranges, p.nwt, p.fwords + p.pwords, e);

@@ -16,38 +16,26 @@ void prep_launch(const PrepArgs& a, const dim3 grid, const bool vec, hipStream_t
 #undef PTY_PREP_BIN
 }
 
-// the pass, then the fold of whatever the pass left in work (nothing: one wave tile and one range)
+// the pass, then the fold (FrameFold, host_handle.hpp)
 int do_prepare_frames(float* data, unsigned char* mask, double* frames, double* pixels, const void* raw, int dtype,
                       const long long* index, const float* dark, const float* gain, const unsigned char* bad,
                       long long ptheta, long long nraw, long long nscan, const PrepGeom& g, float sat, float scale,
                       int clip, double* work, hipStream_t st) {
     const long long npix = (long long)g.ndet * g.ndet;
-    const PrepPlan p = prep_plan(ptheta, nscan, npix);
-    double* fpart = p.fwords ? work : frames;
-    double* ppart = p.pwords ? work + p.fwords : pixels;
+    const FrameFold<PrepPart> f(frames, pixels, work, ptheta, nscan, npix);
     // 16-byte stores: every frame starts on a multiple of four pixels and the array on 16 bytes
-    const bool vst = npix % kPrepLanePix == 0 && ((uintptr_t)data & 15u) == 0;
-    const PrepArgs a{data, mask, fpart, ppart, raw, index, dark, gain, bad, g, npix, p.nwt, nraw, (int)nscan,
-                     (int)p.flen, sat, scale, clip, vst ? 1 : 0, pixels ? 1 : 0};
+    const bool vst = npix % PrepPart::kLanePix == 0 && aligned16(data);
+    const PrepArgs a{data, mask, f.fpart, f.ppart, raw, index, dark, gain, bad, g, npix, f.p.nwt, nraw, (int)nscan,
+                     (int)f.p.flen, sat, scale, clip, vst ? 1 : 0, pixels ? 1 : 0};
     const bool vec = vst && prep_runs_aligned(g);
-    const dim3 grid((unsigned)p.ntiles, (unsigned)p.nranges, (unsigned)ptheta);
     switch (dtype) {
-        case kPrepU16: prep_launch<unsigned short>(a, grid, vec, st); break;
-        case kPrepU32: prep_launch<unsigned int>(a, grid, vec, st); break;
-        case kPrepI32: prep_launch<int>(a, grid, vec, st); break;
-        default: prep_launch<float>(a, grid, vec, st); break;
+        case kPrepU16: prep_launch<unsigned short>(a, f.grid(), vec, st); break;
+        case kPrepU32: prep_launch<unsigned int>(a, f.grid(), vec, st); break;
+        case kPrepI32: prep_launch<int>(a, f.grid(), vec, st); break;
+        default: prep_launch<float>(a, f.grid(), vec, st); break;
     }
     HIP_TRY(hipGetLastError());
-    const long long nfout = p.fwords ? ptheta * nscan * kPrepCols : 0;
-    const long long npout = p.pwords && pixels ? ptheta * kPrepMaps * npix : 0;
-    const long long fblocks = (nfout + 255) / 256, pblocks = (npout + 255) / 256;
-    if (fblocks + pblocks > 0) {
-        hipLaunchKernelGGL(k_prepare_fold, dim3((unsigned)(fblocks + pblocks)), dim3(256), 0, st, frames, pixels,
-                           (const double*)fpart, (const double*)ppart, nfout, p.nwt, npout, npix, p.nranges,
-                           (unsigned)fblocks);
-        HIP_TRY(hipGetLastError());
-    }
-    return PTYCHO_OK;
+    return f.fold(k_prepare_fold, npix, st);
 }
 
 }  // namespace

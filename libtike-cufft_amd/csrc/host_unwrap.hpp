@@ -15,7 +15,7 @@ bool unwrap_sizes_ok(size_t ptheta, size_t nz, size_t n) {
 bool unwrap_vec(int n, std::initializer_list<const void*> ptrs) {
     if (n % kUnwVec != 0) return false;
     for (const void* p : ptrs)
-        if (p && (reinterpret_cast<uintptr_t>(p) & 15u) != 0) return false;
+        if (p && !aligned16(p)) return false;
     return true;
 }
 

@@ -3,7 +3,7 @@
 //
 //   k_fit_accumulate  inten = |g|^2 or inten += |g|^2, four elements per thread (16-byte loads where the pointers allow).
 //   k_fit_frames      one pass over farplane / intensity and data.  A workgroup (four independent waves, no barrier) owns
-//                     a tile of kFitTile pixels and one range of frames of its angle; a lane owns two groups of four
+//                     a tile of FitPart::kTile pixels and one range of frames of its angle; a lane owns two groups of four
 //                     consecutive pixels (one 16-byte load of data / intensity, two of the farplane, per group and
 //                     frame), the next frame's loads issued before this frame's arithmetic.  An unmeasured pixel gets
 //                     I = d = 0 by a select.  Terms in float32, every accumulation in float64:
@@ -18,42 +18,20 @@
 //                     alone, never on the range or on the other frames.
 //   k_fit_fold        adds the wave tiles of every frame and the ranges of every pixel in index order.
 //
-// The partition (fit_plan, fit_pixel, the slots of `work`) is plain C++: tests/test_fit_cpu.py builds host_fit.cpp with
-// the host compiler and checks that every (frame, pixel) pair and every word of `work` is visited exactly once.
+// The partition and the words of `work` are FitPart, an instance of frame_part.hpp's plain C++: tests/test_fit_cpu.py
+// builds host_fit.cpp with the host compiler and checks that every (frame, pixel) pair and every word of `work` is
+// visited exactly once.
 #pragma once
 
-#ifndef PTY_HD
-#if defined(__HIPCC__)
-#define PTY_HD __host__ __device__
-#else
-#define PTY_HD inline
-#endif
-#endif
+#include "frame_part.hpp"
 
 namespace pty {
 
-constexpr int kFitLanePix = 4;                               // consecutive pixels of one 16-byte load of data
-constexpr int kFitGroups = 2;                                // such groups per lane
-constexpr int kFitSlots = kFitLanePix * kFitGroups;          // pixels per lane
-constexpr int kFitGroupSpan = 64 * kFitLanePix;              // pixels one load instruction of a wave covers
-constexpr int kFitWaveTile = kFitGroupSpan * kFitGroups;     // 512 pixels per wave
-constexpr int kFitWaves = 4;
-constexpr int kFitTile = kFitWaveTile * kFitWaves;           // 2048 pixels per workgroup
-constexpr int kFitCols = 8, kFitMaps = 4;
-constexpr long long kFitMinRange = 128;                      // frames: at most ceil(nscan / 128) ranges
-constexpr long long kFitTargetGroups = 2048;                 // workgroups wanted: 256 compute units, eight each
+// two groups of four pixels per lane: 512 pixels per wave, 2048 per workgroup; eight sums per frame, four maps
+using FitPart = FramePart<4, 2, 8, 4>;
 constexpr unsigned long long kFitMaxAngles = 65535;          // gridDim.z
 constexpr unsigned long long kFitMaxDim = 0x7fffffffull;     // nscan, npix
 constexpr unsigned long long kFitMaxElems = 1ull << 59;      // ptheta * nscan * npix: byte offsets stay in 64 bits
-
-struct FitPlan {
-    long long nwt;       // wave tiles per frame
-    long long ntiles;    // workgroup tiles per frame
-    long long nranges;   // frame ranges per angle
-    long long flen;      // frames per range (the last one may be shorter)
-    long long fwords;    // float64 words of per-(frame, wave tile) partials, 0: the kernel writes `frames` itself
-    long long pwords;    // float64 words of per-(range, map, pixel) partials, 0: the kernel writes `pixels` itself
-};
 
 PTY_HD bool fit_sizes_ok(const unsigned long long ptheta, const unsigned long long nscan, const unsigned long long npix) {
     if (ptheta == 0 || nscan == 0 || npix == 0) return false;
@@ -62,39 +40,7 @@ PTY_HD bool fit_sizes_ok(const unsigned long long ptheta, const unsigned long lo
     return true;
 }
 
-// sizes must have passed fit_sizes_ok
-PTY_HD FitPlan fit_plan(const long long ptheta, const long long nscan, const long long npix) {
-    FitPlan p;
-    p.nwt = (npix + kFitWaveTile - 1) / kFitWaveTile;
-    p.ntiles = (npix + kFitTile - 1) / kFitTile;
-    const long long per_range = ptheta * p.ntiles;
-    long long nr = (kFitTargetGroups + per_range - 1) / per_range;
-    const long long most = (nscan + kFitMinRange - 1) / kFitMinRange;
-    if (nr > most) nr = most;
-    p.flen = (nscan + nr - 1) / nr;
-    p.nranges = (nscan + p.flen - 1) / p.flen;
-    p.fwords = p.nwt > 1 ? ptheta * nscan * p.nwt * kFitCols : 0;
-    p.pwords = p.nranges > 1 ? ptheta * p.nranges * kFitMaps * npix : 0;
-    return p;
-}
-
-// first pixel of group h of lane `lane` of wave tile wt; the group is the four pixels from there
-PTY_HD long long fit_pixel(const long long wt, const int lane, const int h) {
-    return wt * kFitWaveTile + (long long)h * kFitGroupSpan + (long long)lane * kFitLanePix;
-}
-// word of the partial sums of (frame, wave tile) in the frame part of `work` (frame counts over all angles)
-PTY_HD long long fit_frame_word(const long long frame, const long long wt, const long long nwt) {
-    return (frame * nwt + wt) * kFitCols;
-}
-// word of pixel 0 of (angle, range, map) in the pixel part of `work`
-PTY_HD long long fit_pixel_word(const long long t, const long long r, const int map, const long long nranges,
-                                const long long npix) {
-    return ((t * nranges + r) * kFitMaps + map) * npix;
-}
-
 #if defined(__HIPCC__)
-
-typedef float fit_f4 __attribute__((ext_vector_type(4)));
 
 // v_sqrt_f32 / v_log_f32 (1 ulp), as k_rows.hpp
 __device__ __forceinline__ float fit_sqrt(const float x) { return __builtin_amdgcn_sqrtf(x); }
@@ -114,14 +60,14 @@ __global__ __launch_bounds__(256) void k_fit_accumulate(float* __restrict__ inte
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= count) return;
     if (vec && i + 4 <= count) {
-        const fit_f4 g0 = *(const fit_f4*)(g + i), g1 = *(const fit_f4*)(g + i + 2);
-        fit_f4 v = fit_f4{fit_abs2(c32{g0.x, g0.y}), fit_abs2(c32{g0.z, g0.w}), fit_abs2(c32{g1.x, g1.y}),
-                          fit_abs2(c32{g1.z, g1.w})};
+        const vec4f g0 = *(const vec4f*)(g + i), g1 = *(const vec4f*)(g + i + 2);
+        vec4f v = vec4f{fit_abs2(c32{g0.x, g0.y}), fit_abs2(c32{g0.z, g0.w}), fit_abs2(c32{g1.x, g1.y}),
+                        fit_abs2(c32{g1.z, g1.w})};
         if (add) {
 #pragma clang fp contract(off)
-            v = *(const fit_f4*)(inten + i) + v;
+            v = *(const vec4f*)(inten + i) + v;
         }
-        *(fit_f4*)(inten + i) = v;
+        *(vec4f*)(inten + i) = v;
     } else {
         for (size_t k = i; k < i + 4 && k < count; ++k) {
 #pragma clang fp contract(off)
@@ -144,43 +90,43 @@ struct FitArgs {
 };
 
 struct FitRaw {
-    float in[kFitSlots];   // intensity of the other modes
-    c32 g[kFitSlots];
-    float d[kFitSlots];
+    float in[FitPart::kSlots];   // intensity of the other modes
+    c32 g[FitPart::kSlots];
+    float d[FitPart::kSlots];
 };
 
 // the lane's eight pixels of the frame that starts at element `base`.  Nothing is predicated: a pixel past the end of the
 // detector (live[q] false; with VEC, npix % 4 == 0, a group is inside or outside as a whole) reads pixel 0 of the frame
 // instead, and the caller drops it as it drops an unmeasured pixel
 template <bool VEC>
-__device__ __forceinline__ FitRaw fit_load(const FitArgs& a, const size_t base, const long long (&p0)[kFitGroups],
-                                           const bool (&live)[kFitSlots]) {
+__device__ __forceinline__ FitRaw fit_load(const FitArgs& a, const size_t base, const long long (&p0)[FitPart::kGroups],
+                                           const bool (&live)[FitPart::kSlots]) {
     FitRaw r;
 #pragma unroll
-    for (int q = 0; q < kFitSlots; ++q) {
+    for (int q = 0; q < FitPart::kSlots; ++q) {
         r.in[q] = 0.0f;
         r.g[q] = c32{0.0f, 0.0f};
     }
 #pragma unroll
-    for (int h = 0; h < kFitGroups; ++h) {
+    for (int h = 0; h < FitPart::kGroups; ++h) {
         if constexpr (VEC) {
-            const size_t at = base + (size_t)(live[h * kFitLanePix] ? p0[h] : 0);
-            const fit_f4 d = __builtin_nontemporal_load((const fit_f4*)(a.data + at));
+            const size_t at = base + (size_t)(live[h * FitPart::kLanePix] ? p0[h] : 0);
+            const vec4f d = __builtin_nontemporal_load((const vec4f*)(a.data + at));
             r.d[4 * h] = d.x; r.d[4 * h + 1] = d.y; r.d[4 * h + 2] = d.z; r.d[4 * h + 3] = d.w;
             if (a.inten) {
-                const fit_f4 v = __builtin_nontemporal_load((const fit_f4*)(a.inten + at));
+                const vec4f v = __builtin_nontemporal_load((const vec4f*)(a.inten + at));
                 r.in[4 * h] = v.x; r.in[4 * h + 1] = v.y; r.in[4 * h + 2] = v.z; r.in[4 * h + 3] = v.w;
             }
             if (a.g) {
-                const fit_f4 g0 = __builtin_nontemporal_load((const fit_f4*)(a.g + at));
-                const fit_f4 g1 = __builtin_nontemporal_load((const fit_f4*)(a.g + at + 2));
+                const vec4f g0 = __builtin_nontemporal_load((const vec4f*)(a.g + at));
+                const vec4f g1 = __builtin_nontemporal_load((const vec4f*)(a.g + at + 2));
                 r.g[4 * h] = c32{g0.x, g0.y}; r.g[4 * h + 1] = c32{g0.z, g0.w};
                 r.g[4 * h + 2] = c32{g1.x, g1.y}; r.g[4 * h + 3] = c32{g1.z, g1.w};
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < kFitLanePix; ++k) {
-                const int q = h * kFitLanePix + k;
+            for (int k = 0; k < FitPart::kLanePix; ++k) {
+                const int q = h * FitPart::kLanePix + k;
                 const size_t at = base + (size_t)(live[q] ? p0[h] + k : 0);
                 r.d[q] = a.data[at];
                 if (a.inten) r.in[q] = a.inten[at];
@@ -195,7 +141,7 @@ __device__ __forceinline__ FitRaw fit_load(const FitArgs& a, const size_t base, 
 // unmeasured pixel is given I = 0 and d = 0 by a select, not a product (it may hold anything), which makes every term
 // an exact zero
 __device__ __forceinline__ void fit_terms(const float inten, const c32 g, const float data, const float s2,
-                                          const bool meas, float (&t)[kFitCols], float& diff) {
+                                          const bool meas, float (&t)[FitPart::kCols], float& diff) {
 #pragma clang fp contract(off)
     const float I = meas ? (inten + fit_abs2(g)) * s2 : 0.0f, d = meas ? data : 0.0f;
     const float sI = fit_sqrt(I), sd = fit_sqrt(d);
@@ -213,7 +159,7 @@ __device__ __forceinline__ void fit_terms(const float inten, const c32 g, const 
 // of f[0 .. N): keep = f[k] or f[k + N / 2] by `hi`, the other half goes to the lane at distance `o` and its counterpart
 // comes back
 template <int N>
-__device__ __forceinline__ void fit_halve(double (&f)[kFitCols], const bool hi, const int o) {
+__device__ __forceinline__ void fit_halve(double (&f)[FitPart::kCols], const bool hi, const int o) {
 #pragma unroll
     for (int k = 0; k < N / 2; ++k) {
         const double keep = hi ? f[k + N / 2] : f[k], send = hi ? f[k] : f[k + N / 2];
@@ -223,18 +169,18 @@ __device__ __forceinline__ void fit_halve(double (&f)[kFitCols], const bool hi, 
 
 // one frame of one wave: the lane's pixels into pacc and into the eight sums, the sums over the wave, the store to dst
 template <bool PIX>
-__device__ __forceinline__ void fit_frame(const FitRaw& raw, const float s2, const bool (&meas)[kFitSlots],
-                                          double (&pacc)[PIX ? kFitMaps : 1][kFitSlots], const int lane,
+__device__ __forceinline__ void fit_frame(const FitRaw& raw, const float s2, const bool (&meas)[FitPart::kSlots],
+                                          double (&pacc)[PIX ? FitPart::kMaps : 1][FitPart::kSlots], const int lane,
                                           double* __restrict__ dst) {
-    double f[kFitCols];
+    double f[FitPart::kCols];
 #pragma unroll
-    for (int e = 0; e < kFitCols; ++e) f[e] = 0.0;
+    for (int e = 0; e < FitPart::kCols; ++e) f[e] = 0.0;
 #pragma unroll
-    for (int q = 0; q < kFitSlots; ++q) {
-        float tm[kFitCols], diff;
+    for (int q = 0; q < FitPart::kSlots; ++q) {
+        float tm[FitPart::kCols], diff;
         fit_terms(raw.in[q], raw.g[q], raw.d[q], s2, meas[q], tm, diff);
 #pragma unroll
-        for (int e = 0; e < kFitCols; ++e) f[e] += (double)tm[e];
+        for (int e = 0; e < FitPart::kCols; ++e) f[e] += (double)tm[e];
         if constexpr (PIX) {
             pacc[0][q] += (double)tm[0];
             pacc[1][q] += (double)tm[1];
@@ -257,16 +203,16 @@ __device__ __forceinline__ void fit_frame(const FitRaw& raw, const float s2, con
 template <bool VEC, bool PIX>
 __global__ __launch_bounds__(256) void k_fit_frames(const FitArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long wt = (long long)blockIdx.x * kFitWaves + wave;
+    const long long wt = (long long)blockIdx.x * FitPart::kWaves + wave;
     if (wt >= a.nwt) return;   // waves are independent: no barrier below
     const long long r = blockIdx.y, t = blockIdx.z, npix = a.npix;
-    long long p0[kFitGroups];
-    bool live[kFitSlots], meas[kFitSlots];
+    long long p0[FitPart::kGroups];
+    bool live[FitPart::kSlots], meas[FitPart::kSlots];
 #pragma unroll
-    for (int h = 0; h < kFitGroups; ++h) p0[h] = fit_pixel(wt, lane, h);
+    for (int h = 0; h < FitPart::kGroups; ++h) p0[h] = FitPart::pixel(wt, lane, h);
 #pragma unroll
-    for (int q = 0; q < kFitSlots; ++q) {
-        const long long p = p0[q / kFitLanePix] + q % kFitLanePix;
+    for (int q = 0; q < FitPart::kSlots; ++q) {
+        const long long p = p0[q / FitPart::kLanePix] + q % FitPart::kLanePix;
         live[q] = p < npix;
         meas[q] = live[q] && (a.mask == nullptr || a.mask[p] != 0);
     }
@@ -277,55 +223,40 @@ __global__ __launch_bounds__(256) void k_fit_frames(const FitArgs a) {
     }
     const int j0 = (int)r * a.flen, j1 = j0 + a.flen < a.nscan ? j0 + a.flen : a.nscan;
     const size_t frame0 = (size_t)t * (size_t)a.nscan, snpix = (size_t)npix;
-    double pacc[PIX ? kFitMaps : 1][kFitSlots];
+    double pacc[PIX ? FitPart::kMaps : 1][FitPart::kSlots];
 #pragma unroll
-    for (int m = 0; m < (PIX ? kFitMaps : 1); ++m)
+    for (int m = 0; m < (PIX ? FitPart::kMaps : 1); ++m)
 #pragma unroll
-        for (int q = 0; q < kFitSlots; ++q) pacc[m][q] = 0.0;
+        for (int q = 0; q < FitPart::kSlots; ++q) pacc[m][q] = 0.0;
 
     // two buffers, frames alternate between them: a frame's loads are issued before the arithmetic of the frame before it
     FitRaw ra = fit_load<VEC>(a, (frame0 + (size_t)j0) * snpix, p0, live), rb = ra;
     for (int j = j0; j < j1; j += 2) {
         const size_t frame = frame0 + (size_t)j;
         if (j + 1 < j1) rb = fit_load<VEC>(a, (frame + 1) * snpix, p0, live);
-        fit_frame<PIX>(ra, s2, meas, pacc, lane, a.fpart + fit_frame_word((long long)frame, wt, a.nwt));
+        fit_frame<PIX>(ra, s2, meas, pacc, lane, a.fpart + FitPart::frame_word((long long)frame, wt, a.nwt));
         if (j + 1 >= j1) break;
         if (j + 2 < j1) ra = fit_load<VEC>(a, (frame + 2) * snpix, p0, live);
-        fit_frame<PIX>(rb, s2, meas, pacc, lane, a.fpart + fit_frame_word((long long)frame + 1, wt, a.nwt));
+        fit_frame<PIX>(rb, s2, meas, pacc, lane, a.fpart + FitPart::frame_word((long long)frame + 1, wt, a.nwt));
     }
     if constexpr (PIX) {
 #pragma unroll
-        for (int m = 0; m < kFitMaps; ++m) {
-            double* dst = a.ppart + fit_pixel_word(t, r, m, gridDim.y, npix);
+        for (int m = 0; m < FitPart::kMaps; ++m) {
+            double* dst = a.ppart + FitPart::pixel_word(t, r, m, gridDim.y, npix);
 #pragma unroll
-            for (int q = 0; q < kFitSlots; ++q)
-                if (live[q]) dst[p0[q / kFitLanePix] + q % kFitLanePix] = pacc[m][q];
+            for (int q = 0; q < FitPart::kSlots; ++q)
+                if (live[q]) dst[p0[q / FitPart::kLanePix] + q % FitPart::kLanePix] = pacc[m][q];
         }
     }
 }
 
-// grid fblocks + pblocks, 256 threads: the first fblocks workgroups add the wave tiles of ptheta * nscan * 8 frame sums,
-// the others the ranges of ptheta * 4 * npix pixel sums, both in index order
+// FramePart::fold, every column a sum; slab = 4 npix
 __global__ __launch_bounds__(256) void k_fit_fold(double* __restrict__ frames, double* __restrict__ pixels,
                                                   const double* __restrict__ fpart, const double* __restrict__ ppart,
                                                   const long long nfout, const long long nwt, const long long npout,
                                                   const long long slab, const long long nranges,
                                                   const unsigned fblocks) {
-    if (blockIdx.x < fblocks) {
-        const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-        if (i >= nfout) return;
-        const long long frame = i / kFitCols, e = i % kFitCols;
-        double s = 0.0;
-        for (long long w = 0; w < nwt; ++w) s += fpart[fit_frame_word(frame, w, nwt) + e];
-        frames[i] = s;
-    } else {
-        const long long i = (long long)(blockIdx.x - fblocks) * 256 + threadIdx.x;
-        if (i >= npout) return;
-        const long long t = i / slab, rem = i % slab;   // slab = 4 npix: (map, pixel) of one angle and range
-        double s = 0.0;
-        for (long long r = 0; r < nranges; ++r) s += ppart[(t * nranges + r) * slab + rem];
-        pixels[i] = s;
-    }
+    FitPart::fold<-1>(frames, pixels, fpart, ppart, nfout, nwt, npout, slab, nranges, fblocks);
 }
 
 #endif  // __HIPCC__

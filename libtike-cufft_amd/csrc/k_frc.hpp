@@ -19,13 +19,7 @@
 
 #include <cmath>
 
-#ifndef PTY_HD
-#if defined(__HIPCC__)
-#define PTY_HD __host__ __device__
-#else
-#define PTY_HD inline
-#endif
-#endif
+#include "frame_part.hpp"
 
 namespace pty {
 

@@ -13,7 +13,7 @@
 //                    loads per pixel and position, all L1 / L2 hits.  Each pixel is written once: no zeroing pass.
 //   k_gauge_sums     pass 1 of the fit: workgroup b of angle t owns rows b, b + nb, ..; per thread float64 sums of
 //                    {Cx, Cy, W, sum w y, sum w x, sum w |psi|^2, sum w |ref|^2}, a shuffle tree per wave, the four
-//                    waves added in order (as k_frc_rings), one row of `work` per workgroup.
+//                    waves added in order (block_sum, frame_part.hpp), one row of `work` per workgroup.
 //   k_gauge_finish   stage 1: adds the rows in a fixed order and writes (gy, gx, 0, s, yc, xc) to gauge[t];
 //                    stage 2: the same for pass 2's rows and writes phi0.
 //   k_gauge_offset   pass 2: Z = sum w u exp(-i (gy (y - yc) + gx (x - xc))), the ramp read from gauge[t] on the device,
@@ -26,13 +26,7 @@
 
 #include <cmath>
 
-#ifndef PTY_HD
-#if defined(__HIPCC__)
-#define PTY_HD __host__ __device__
-#else
-#define PTY_HD inline
-#endif
-#endif
+#include "frame_part.hpp"
 
 namespace pty {
 
@@ -163,24 +157,6 @@ __global__ __launch_bounds__(256) void k_illumination(float* __restrict__ out, c
 }
 
 // ---- gauge fit ----------------------------------------------------------------------------------------------------------
-// v[0 .. NV) of the 256 threads -> dst[0 .. NV): a shuffle tree per wave, then the four waves in order.  part: 4 NV doubles
-template <int NV>
-__device__ __forceinline__ void gauge_block_sum(double (&v)[NV], double* __restrict__ dst, double* part) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v[e] += __shfl_xor(v[e], o);
-    }
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int e = 0; e < NV; ++e) part[wave * NV + e] = v[e];
-    }
-    __syncthreads();
-    if (tid < NV) dst[tid] = ((part[tid] + part[NV + tid]) + part[2 * NV + tid]) + part[3 * NV + tid];
-}
-
 struct GaugePix {
     double ur, ui, w, p2, r2;
 };
@@ -242,7 +218,7 @@ __global__ __launch_bounds__(256) void k_gauge_sums(double* __restrict__ work, c
             }
         }
     }
-    gauge_block_sum<9>(v, work + ((size_t)t * kGaugeMaxBlocks + blockIdx.x) * kGaugeStride, part);
+    block_sum<9>(v, work + ((size_t)t * kGaugeMaxBlocks + blockIdx.x) * kGaugeStride, part);
 }
 
 // exp(2 pi i turns), turns reduced to [-1/2, 1/2] first
@@ -278,7 +254,7 @@ __global__ __launch_bounds__(256) void k_gauge_offset(double* __restrict__ work,
             v[1] += g.w * (g.ui * cs - g.ur * sn);
         }
     }
-    gauge_block_sum<2>(v, work + ((size_t)t * kGaugeMaxBlocks + blockIdx.x) * kGaugeStride + 9, part);
+    block_sum<2>(v, work + ((size_t)t * kGaugeMaxBlocks + blockIdx.x) * kGaugeStride + 9, part);
 }
 
 __device__ __forceinline__ double gauge_arg(const double re, const double im) {
@@ -299,7 +275,7 @@ __global__ __launch_bounds__(256) void k_gauge_finish(double* __restrict__ gauge
 #pragma unroll
             for (int e = 0; e < 9; ++e) v[e] += rows[(size_t)b * kGaugeStride + e];
         }
-        gauge_block_sum<9>(v, tot, part);
+        block_sum<9>(v, tot, part);
         __syncthreads();
         if (tid == 0) {
             const double W = tot[4];
@@ -320,7 +296,7 @@ __global__ __launch_bounds__(256) void k_gauge_finish(double* __restrict__ gauge
             v[0] += rows[(size_t)b * kGaugeStride + 9];
             v[1] += rows[(size_t)b * kGaugeStride + 10];
         }
-        gauge_block_sum<2>(v, tot, part);
+        block_sum<2>(v, tot, part);
         __syncthreads();
         if (tid == 0) g[2] = gauge_arg(tot[0], tot[1]);
     }

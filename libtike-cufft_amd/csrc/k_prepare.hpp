@@ -3,8 +3,8 @@
 // [0, 0] (ifftshift), and per-frame / per-pixel statistics, in one pass that reads every raw byte once.  No handle, no
 // atomics, every sum in a fixed order: the same inputs give the same bits.
 //
-//   k_prepare       A workgroup (four independent waves, no barrier) owns a tile of kPrepTile OUTPUT pixels (indices in the
-//                   layout of `data`) and one range of frames of its angle; a lane owns one group of four consecutive
+//   k_prepare       A workgroup (four independent waves, no barrier) owns a tile of PrepPart::kTile OUTPUT pixels (indices
+//                   in the layout of `data`) and one range of frames of its angle; a lane owns one group of four consecutive
 //                   output pixels: one 16-byte store of data per frame.  VEC (ndet % 8 == 0, W % 4 == 0,
 //                   x0 % 4 == 0, raw aligned to four elements): the shift leaves the four pixels of a group consecutive in
 //                   the raw row and a run of four raw elements wholly inside or outside the frame, so a group reads
@@ -21,31 +21,19 @@
 //   k_prepare_fold  combines the wave tiles of every frame and the ranges of every pixel in index order: sums and counts
 //                   are added, maxima taken.
 //
-// The partition (prep_plan, prep_pixel, the words of `work`) and the crop / shift index map (prep_centred,
-// prep_raw_offset) are plain C++: host_prepare.cpp walks them on the CPU.
+// The partition and the words of `work` are PrepPart, an instance of frame_part.hpp's plain C++, over OUTPUT pixels; the
+// store lanes (prep_lane_col) and the crop / shift index map (prep_centred, prep_raw_offset) are plain C++ too:
+// host_prepare.cpp walks them on the CPU.
 #pragma once
 
-#ifndef PTY_HD
-#if defined(__HIPCC__)
-#define PTY_HD __host__ __device__
-#else
-#define PTY_HD inline
-#endif
-#endif
+#include "frame_part.hpp"
 
 namespace pty {
 
-constexpr int kPrepLanePix = 4;                                // consecutive output pixels of one 16-byte store
-constexpr int kPrepGroups = 1;                                 // such groups per lane
-constexpr int kPrepSlots = kPrepLanePix * kPrepGroups;         // output pixels per lane
-constexpr int kPrepGroupSpan = 64 * kPrepLanePix;              // pixels one store instruction of a wave covers
-constexpr int kPrepWaveTile = kPrepGroupSpan * kPrepGroups;    // 256 pixels per wave
-constexpr int kPrepWaves = 4;
-constexpr int kPrepTile = kPrepWaveTile * kPrepWaves;          // 1024 pixels per workgroup
-constexpr int kPrepCols = 4, kPrepMaps = 4;                    // sum, sum of squares, maximum, saturation count
+// one group of four output pixels per lane: 256 pixels per wave, 1024 per workgroup; per frame and per pixel the sum,
+// the sum of squares, the maximum and the saturation count
+using PrepPart = FramePart<4, 1, 4, 4>;
 constexpr int kPrepMaxCol = 2;                                 // the column / map that is folded with max, not +
-constexpr long long kPrepMinRange = 128;                       // frames: at most ceil(nscan / 128) ranges
-constexpr long long kPrepTargetGroups = 2048;                  // workgroups wanted: 256 compute units, eight each
 constexpr unsigned long long kPrepMaxAngles = 65535;           // gridDim.z
 constexpr unsigned long long kPrepMaxFrames = 0x7fffffffull;   // nraw, nscan
 constexpr unsigned long long kPrepMaxFrame = 0x7fffffffull;    // H * W: an offset inside a raw frame fits an int
@@ -59,15 +47,6 @@ struct PrepGeom {
     long long H, W;      // raw frame
     long long y0, x0;    // raw row and column of the first pixel of the crop window
     int bin, ndet;
-};
-
-struct PrepPlan {
-    long long nwt;       // wave tiles per frame
-    long long ntiles;    // workgroup tiles per frame
-    long long nranges;   // frame ranges per angle
-    long long flen;      // frames per range (the last one may be shorter)
-    long long fwords;    // float64 words of per-(frame, wave tile) partials, 0: the kernel writes `frames` itself
-    long long pwords;    // float64 words of per-(range, map, pixel) partials, 0: the kernel writes `pixels` itself
 };
 
 PTY_HD bool prep_sizes_ok(const unsigned long long ptheta, const unsigned long long nscan, const unsigned long long npix) {
@@ -86,35 +65,6 @@ PTY_HD bool prep_raw_ok(const unsigned long long ptheta, const unsigned long lon
     return true;
 }
 
-// sizes must have passed prep_sizes_ok
-PTY_HD PrepPlan prep_plan(const long long ptheta, const long long nscan, const long long npix) {
-    PrepPlan p;
-    p.nwt = (npix + kPrepWaveTile - 1) / kPrepWaveTile;
-    p.ntiles = (npix + kPrepTile - 1) / kPrepTile;
-    const long long per_range = ptheta * p.ntiles;
-    long long nr = (kPrepTargetGroups + per_range - 1) / per_range;
-    const long long most = (nscan + kPrepMinRange - 1) / kPrepMinRange;
-    if (nr > most) nr = most;
-    p.flen = (nscan + nr - 1) / nr;
-    p.nranges = (nscan + p.flen - 1) / p.flen;
-    p.fwords = p.nwt > 1 ? ptheta * nscan * p.nwt * kPrepCols : 0;
-    p.pwords = p.nranges > 1 ? ptheta * p.nranges * kPrepMaps * npix : 0;
-    return p;
-}
-
-// first output pixel of group h of lane `lane` of wave tile wt; the group is the four pixels from there
-PTY_HD long long prep_pixel(const long long wt, const int lane, const int h) {
-    return wt * kPrepWaveTile + (long long)h * kPrepGroupSpan + (long long)lane * kPrepLanePix;
-}
-// word of the partials of (frame, wave tile) in the frame part of `work` (frame counts over all angles)
-PTY_HD long long prep_frame_word(const long long frame, const long long wt, const long long nwt) {
-    return (frame * nwt + wt) * kPrepCols;
-}
-// word of pixel 0 of (angle, range, map) in the pixel part of `work`
-PTY_HD long long prep_pixel_word(const long long t, const long long r, const int map, const long long nranges,
-                                 const long long npix) {
-    return ((t * nranges + r) * kPrepMaps + map) * npix;
-}
 // lane (lane & 15 == 0) -> the column it stores after prep_wave_reduce: 0 sum, 1 sum of squares, 3 count, 2 maximum
 PTY_HD int prep_lane_col(const int lane) { return (lane >> 4) == 2 ? 3 : (lane >> 4) == 3 ? 2 : (lane >> 4); }
 
@@ -135,8 +85,6 @@ PTY_HD bool prep_runs_aligned(const PrepGeom& g) {
 }
 
 #if defined(__HIPCC__)
-
-typedef float prep_f4 __attribute__((ext_vector_type(4)));
 
 struct PrepArgs {
     float* data;
@@ -194,7 +142,7 @@ __device__ __forceinline__ void prep_load_group(const T* __restrict__ frame, con
             }
     } else {
 #pragma unroll
-        for (int k = 0; k < kPrepLanePix; ++k)
+        for (int k = 0; k < PrepPart::kLanePix; ++k)
 #pragma unroll
             for (int e = 0; e < BIN * BIN; ++e) rw[k][e] = __builtin_nontemporal_load(frame + off[k][e]);
     }
@@ -238,33 +186,29 @@ __device__ __forceinline__ float prep_value(const T (&rw)[BIN * BIN], const floa
     return v * scale;
 }
 
-__device__ __forceinline__ double prep_mix(const double keep, const double recv, const bool is_max) {
-    return is_max ? fmax(keep, recv) : keep + recv;
-}
-
 // f = {sum, sum of squares, count, maximum} of the lane -> the same over the wave, in lanes 0, 16, 32, 48
 // (prep_lane_col): bits 5 and 4 of the lane pick the half of the vectors that is kept
-__device__ __forceinline__ double prep_wave_reduce(const double (&f)[kPrepCols], const int lane) {
+__device__ __forceinline__ double prep_wave_reduce(const double (&f)[PrepPart::kCols], const int lane) {
     const bool hi = (lane & 32) != 0, hi2 = (lane & 16) != 0, is_max = hi && hi2;
     const double k0 = hi ? f[2] : f[0], s0 = hi ? f[0] : f[2], k1 = hi ? f[3] : f[1], s1 = hi ? f[1] : f[3];
     const double a0 = k0 + __shfl_xor(s0, 32);
-    const double a1 = prep_mix(k1, __shfl_xor(s1, 32), hi);
-    double v = prep_mix(hi2 ? a1 : a0, __shfl_xor(hi2 ? a0 : a1, 16), is_max);
-    v = prep_mix(v, __shfl_xor(v, 8), is_max);
-    v = prep_mix(v, __shfl_xor(v, 4), is_max);
-    v = prep_mix(v, __shfl_xor(v, 2), is_max);
-    v = prep_mix(v, __shfl_xor(v, 1), is_max);
+    const double a1 = sum_or_max(k1, __shfl_xor(s1, 32), hi);
+    double v = sum_or_max(hi2 ? a1 : a0, __shfl_xor(hi2 ? a0 : a1, 16), is_max);
+    v = sum_or_max(v, __shfl_xor(v, 8), is_max);
+    v = sum_or_max(v, __shfl_xor(v, 4), is_max);
+    v = sum_or_max(v, __shfl_xor(v, 2), is_max);
+    v = sum_or_max(v, __shfl_xor(v, 1), is_max);
     return v;
 }
 
 // grid (ntiles, nranges, ptheta), 256 threads
 template <typename T, int BIN, bool VEC>
 __global__ __launch_bounds__(256) void k_prepare(const PrepArgs a) {
-    constexpr int E = BIN * BIN, S = kPrepSlots, G = kPrepGroups, L = kPrepLanePix;
+    constexpr int E = BIN * BIN, S = PrepPart::kSlots, G = PrepPart::kGroups, L = PrepPart::kLanePix;
     constexpr bool KEEP = BIN <= 2;          // calibration in registers over the range, and the next frame's loads early
     constexpr int KS = KEEP ? S : 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long wt = (long long)blockIdx.x * kPrepWaves + wave;
+    const long long wt = (long long)blockIdx.x * PrepPart::kWaves + wave;
     if (wt >= a.nwt) return;   // waves are independent: no barrier below
     const long long r = blockIdx.y, t = blockIdx.z, npix = a.npix;
     long long p0[G];
@@ -272,7 +216,7 @@ __global__ __launch_bounds__(256) void k_prepare(const PrepArgs a) {
     float dk[KS][E], gn[KS][E];
     bool live[S], meas[S];
 #pragma unroll
-    for (int h = 0; h < G; ++h) p0[h] = prep_pixel(wt, lane, h);
+    for (int h = 0; h < G; ++h) p0[h] = PrepPart::pixel(wt, lane, h);
 #pragma unroll
     for (int q = 0; q < S; ++q) {
         const long long p = p0[q / L] + q % L;
@@ -310,7 +254,7 @@ __global__ __launch_bounds__(256) void k_prepare(const PrepArgs a) {
     // one frame of one wave: data, the lane's pixels into the per-pixel and the per-frame statistics, the frame's over the
     // wave, the store of the partials
     auto frame = [&](const T* __restrict__ src, const T (*pre)[E], const bool valid, const int j) __attribute__((always_inline)) {
-        double f[kPrepCols] = {0.0, 0.0, 0.0, -(double)__builtin_inff()};
+        double f[PrepPart::kCols] = {0.0, 0.0, 0.0, -(double)__builtin_inff()};
         float fm = -__builtin_inff();
         int fc = 0;
         float* const out = a.data + (frame0 + (size_t)j) * (size_t)npix;
@@ -351,7 +295,7 @@ __global__ __launch_bounds__(256) void k_prepare(const PrepArgs a) {
                 pc[q] += ns > 0 ? 1 : 0;
             }
             if (VEC || a.vst) {   // npix % 4 == 0: a group is inside or outside the detector as a whole
-                if (live[h * L]) __builtin_nontemporal_store(prep_f4{v4[0], v4[1], v4[2], v4[3]}, (prep_f4*)(out + p0[h]));
+                if (live[h * L]) __builtin_nontemporal_store(vec4f{v4[0], v4[1], v4[2], v4[3]}, (vec4f*)(out + p0[h]));
             } else {
 #pragma unroll
                 for (int k = 0; k < L; ++k)
@@ -362,7 +306,8 @@ __global__ __launch_bounds__(256) void k_prepare(const PrepArgs a) {
         f[3] = (double)fm;
         const double v = prep_wave_reduce(f, lane);
         if ((lane & 15) == 0)
-            a.fpart[prep_frame_word((long long)(frame0 + (size_t)j), wt, a.nwt) + prep_lane_col(lane)] = valid ? v : 0.0;
+            a.fpart[PrepPart::frame_word((long long)(frame0 + (size_t)j), wt, a.nwt) + prep_lane_col(lane)] =
+                valid ? v : 0.0;
     };
 
     if constexpr (KEEP) {
@@ -396,7 +341,7 @@ __global__ __launch_bounds__(256) void k_prepare(const PrepArgs a) {
         }
     }
     if (a.pix) {
-        double* const dst = a.ppart + prep_pixel_word(t, r, 0, gridDim.y, npix);
+        double* const dst = a.ppart + PrepPart::pixel_word(t, r, 0, gridDim.y, npix);
 #pragma unroll
         for (int q = 0; q < S; ++q) {
             if (!live[q]) continue;
@@ -409,29 +354,13 @@ __global__ __launch_bounds__(256) void k_prepare(const PrepArgs a) {
     }
 }
 
-// grid fblocks + pblocks, 256 threads: the first fblocks workgroups combine the wave tiles of ptheta * nscan * 4 frame
-// figures, the others the ranges of ptheta * 4 * npix pixel figures, both in index order from the first one
+// FramePart::fold, the maxima taken and the rest added
 __global__ __launch_bounds__(256) void k_prepare_fold(double* __restrict__ frames, double* __restrict__ pixels,
                                                       const double* __restrict__ fpart, const double* __restrict__ ppart,
                                                       const long long nfout, const long long nwt, const long long npout,
                                                       const long long npix, const long long nranges,
                                                       const unsigned fblocks) {
-    if (blockIdx.x < fblocks) {
-        const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-        if (i >= nfout) return;
-        const long long frame = i / kPrepCols, e = i % kPrepCols;
-        double s = fpart[prep_frame_word(frame, 0, nwt) + e];
-        for (long long w = 1; w < nwt; ++w) s = prep_mix(s, fpart[prep_frame_word(frame, w, nwt) + e], e == kPrepMaxCol);
-        frames[i] = s;
-    } else {
-        const long long i = (long long)(blockIdx.x - fblocks) * 256 + threadIdx.x;
-        if (i >= npout) return;
-        const long long slab = kPrepMaps * npix, t = i / slab, rem = i % slab;   // (map, pixel) of one angle and range
-        double s = ppart[t * nranges * slab + rem];
-        for (long long r = 1; r < nranges; ++r)
-            s = prep_mix(s, ppart[(t * nranges + r) * slab + rem], rem / npix == kPrepMaxCol);
-        pixels[i] = s;
-    }
+    PrepPart::fold<kPrepMaxCol>(frames, pixels, fpart, ppart, nfout, nwt, npout, PrepPart::kMaps * npix, nranges, fblocks);
 }
 
 #endif  // __HIPCC__

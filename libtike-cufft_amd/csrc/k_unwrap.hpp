@@ -29,13 +29,7 @@
 
 #include <cmath>
 
-#ifndef PTY_HD
-#if defined(__HIPCC__)
-#define PTY_HD __host__ __device__
-#else
-#define PTY_HD inline
-#endif
-#endif
+#include "frame_part.hpp"
 
 namespace pty {
 
@@ -109,24 +103,6 @@ __device__ __forceinline__ UnwTile unwrap_tile(const int ntx, const int nz) {
     unwrap_own((int)threadIdx.x, u.by, u.bx, u.y, u.x);
     u.row = u.y < nz;
     return u;
-}
-
-// v[0 .. NV) of the 256 threads -> dst[0 .. NV), as gauge_block_sum (k_gauge.hpp): a shuffle tree, then the waves in order
-template <int NV>
-__device__ __forceinline__ void unwrap_block_sum(double (&v)[NV], double* __restrict__ dst, double* part) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int e = 0; e < NV; ++e) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v[e] += __shfl_xor(v[e], o);
-    }
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int e = 0; e < NV; ++e) part[wave * NV + e] = v[e];
-    }
-    __syncthreads();
-    if (tid < NV) dst[tid] = ((part[tid] + part[NV + tid]) + part[2 * NV + tid]) + part[3 * NV + tid];
 }
 
 // four consecutive floats at idx: one 16-byte access (VEC: idx % 4 == 0 and the base is 16-byte aligned) or four scalar
@@ -215,7 +191,7 @@ __global__ __launch_bounds__(256) void k_unwrap_setup(float* __restrict__ buf, c
         unwrap_store4<VEC>(base + 2 * plane, idx, z, have);         // p
         unwrap_store4<VEC>(base + 5 * plane, idx, mi, have);        // 1 / D
     }
-    unwrap_block_sum<1>(v, work + ((size_t)t * gridDim.x + blockIdx.x) * kUnwPart, part);
+    block_sum<1>(v, work + ((size_t)t * gridDim.x + blockIdx.x) * kUnwPart, part);
 }
 
 // grid (tiles, ptheta), 256 threads
@@ -287,7 +263,7 @@ __global__ __launch_bounds__(256) void k_unwrap_apply(float* __restrict__ buf, c
         unwrap_store4<VEC>(pnew, idx, p, have);
         unwrap_store4<VEC>(q_, idx, q, have);
     }
-    unwrap_block_sum<1>(v, work + ((size_t)t * gridDim.x + blockIdx.x) * kUnwPart, part);
+    block_sum<1>(v, work + ((size_t)t * gridDim.x + blockIdx.x) * kUnwPart, part);
 }
 
 // the thread's four consecutive pixels of the flat kernels: first index and how many are inside the plane
@@ -326,7 +302,7 @@ __global__ __launch_bounds__(256) void k_unwrap_update(float* __restrict__ buf, 
         unwrap_store4<VEC>(base, idx, x, have);
         unwrap_store4<VEC>(base + plane, idx, r, have);
     }
-    unwrap_block_sum<1>(v, work + ((size_t)t * (size_t)tiles + blockIdx.x) * kUnwPart, part);
+    block_sum<1>(v, work + ((size_t)t * (size_t)tiles + blockIdx.x) * kUnwPart, part);
 }
 
 // grid (ceil(nz n / 1024), ptheta), 256 threads: parts of sum w' [D > 0] exp(i (phi - x))
@@ -357,7 +333,7 @@ __global__ __launch_bounds__(256) void k_unwrap_offset(const float* __restrict__
             }
         }
     }
-    unwrap_block_sum<2>(v, work + ((size_t)t * (size_t)tiles + blockIdx.x) * kUnwPart, part);
+    block_sum<2>(v, work + ((size_t)t * (size_t)tiles + blockIdx.x) * kUnwPart, part);
 }
 
 // grid (ceil(nz n / 1024), ptheta), 256 threads
@@ -400,7 +376,7 @@ __global__ __launch_bounds__(256) void k_unwrap_scalars(double* __restrict__ sta
             v[0] += w[(size_t)b * kUnwPart];
             if (stage == 3) v[1] += w[(size_t)b * kUnwPart + 1];
         }
-        unwrap_block_sum<2>(v, tot, part);
+        block_sum<2>(v, tot, part);
         __syncthreads();
     }
     if (tid != 0) return;

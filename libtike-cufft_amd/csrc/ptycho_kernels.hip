@@ -22,9 +22,10 @@
 // 4096 x 256^2 that is a single pair).
 //
 // Reading order: ptycho_common.hpp first (arguments, and what the run-structured column kernels share: run bounds and
-// decode, tile address, accumulate; run_split.hpp is the host's half of the run structure), then the kernel headers (k_*.hpp), then
+// decode, tile address, accumulate; run_split.hpp is the host's half of the run structure), then the kernel headers (k_*.hpp;
+// frame_part.hpp before the analysis ones, which share its (frame, pixel) partition, fold and block sum), then
 // the host side by topic -- host_handle.hpp (handle, errors, profiler,
-// allocations, dispatch macros), host_ops.hpp (launchers and the three operators), host_cg.hpp (CG stages) -- and
+// allocations, dispatch macros, the host's half of the partition), host_ops.hpp (launchers and the three operators), host_cg.hpp (CG stages) -- and
 // below them nothing but the exported functions: argument checks in the order the tests rely on, then one call.
 #include <hip/hip_runtime.h>
 
@@ -768,9 +769,7 @@ int ptycho_fit_accumulate(float* inten, const void* g, size_t count, int add, vo
 }
 
 size_t ptycho_fit_work_words(size_t ptheta, size_t nscan, size_t npix) {
-    if (!fit_sizes_ok(ptheta, nscan, npix)) return 0;
-    const FitPlan p = fit_plan((long long)ptheta, (long long)nscan, (long long)npix);
-    return (size_t)(p.fwords + p.pwords);
+    return frame_work_words<FitPart>(fit_sizes_ok(ptheta, nscan, npix), ptheta, nscan, npix);
 }
 
 int ptycho_fit_frames(double* frames, double* pixels, const float* inten, const void* g, const float* data,
@@ -781,7 +780,7 @@ int ptycho_fit_frames(double* frames, double* pixels, const float* inten, const 
     if (ptheta == 0 || nscan == 0 || npix == 0) return fail(PTYCHO_ERR_ARG, "all sizes must be positive");
     if (ptheta > kFitMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
     if (!fit_sizes_ok(ptheta, nscan, npix) ||
-        (ptheta * nscan * kFitCols + ptheta * kFitMaps * npix) / 256 + 2 > 0x7fffffffull)
+        (ptheta * nscan * FitPart::kCols + ptheta * FitPart::kMaps * npix) / 256 + 2 > 0x7fffffffull)
         return fail(PTYCHO_ERR_ARG, "nscan, npix or their product with ptheta too large for one launch");
     return do_fit_frames(frames, pixels, inten, (const c32*)g, data, mask, ab, (long long)ptheta, (long long)nscan,
                          (long long)npix, work, (hipStream_t)stream);
@@ -789,9 +788,7 @@ int ptycho_fit_frames(double* frames, double* pixels, const float* inten, const 
 
 // ---- raw detector frames to solver data (k_prepare.hpp, libtike.hipfft.prepare): no handle -------------------------------
 size_t ptycho_prepare_work_words(size_t ptheta, size_t nscan, size_t npix) {
-    if (!prep_sizes_ok(ptheta, nscan, npix)) return 0;
-    const PrepPlan p = prep_plan((long long)ptheta, (long long)nscan, (long long)npix);
-    return (size_t)(p.fwords + p.pwords);
+    return frame_work_words<PrepPart>(prep_sizes_ok(ptheta, nscan, npix), ptheta, nscan, npix);
 }
 
 int ptycho_prepare_frames(float* data, unsigned char* mask, double* frames, double* pixels, const void* raw, int dtype,
@@ -809,7 +806,7 @@ int ptycho_prepare_frames(float* data, unsigned char* mask, double* frames, doub
     if (!index && nraw != nscan) return fail(PTYCHO_ERR_ARG, "without an index nraw must equal nscan");
     if (ndet > kPrepMaxNdet || !prep_sizes_ok(ptheta, nscan, ndet * ndet) || !prep_raw_ok(ptheta, nraw, H, W) ||
         y0 < -kPrepMaxOrigin || y0 > kPrepMaxOrigin || x0 < -kPrepMaxOrigin || x0 > kPrepMaxOrigin ||
-        (ptheta * nscan * kPrepCols + ptheta * kPrepMaps * ndet * ndet) / 256 + 2 > 0x7fffffffull)
+        (ptheta * nscan * PrepPart::kCols + ptheta * PrepPart::kMaps * ndet * ndet) / 256 + 2 > 0x7fffffffull)
         return fail(PTYCHO_ERR_ARG, "sizes, window origin or their products too large for one launch");
     const PrepGeom g{(long long)H, (long long)W, y0, x0, bin, (int)ndet};
     return do_prepare_frames(data, mask, frames, pixels, raw, dtype, index, dark, gain, bad, (long long)ptheta,

@@ -27,7 +27,7 @@ import numbers
 import torch
 
 from . import _native as nat
-from .gauge import _array, _device
+from ._args import _array, _check_out, _device, _need_array, _opt
 from .operators import _ptr, _stream
 
 __all__ = ["fit_frames", "accumulate_intensity", "flag_frames", "check_fit_frames"]
@@ -45,8 +45,7 @@ def check_fit_frames(data, farplane=None, intensity=None, mask=None, ab=None):
     if intensity is not None and _array(intensity, "intensity", "float32", (4,)) != shape:
         raise ValueError("intensity must have data's shape %s, got %s" % (shape, tuple(intensity.shape)))
     if mask is not None:
-        if not hasattr(mask, "shape") or not hasattr(mask, "dtype"):
-            raise TypeError("mask must be an array, got %s" % type(mask).__name__)
+        _need_array(mask, "mask")
         if tuple(int(v) for v in mask.shape) != shape[-2:]:
             raise ValueError("mask must be %s, got shape %s" % (shape[-2:], tuple(mask.shape)))
     if ab is not None and _array(ab, "ab", "float64", (1,)) != (2,):
@@ -65,10 +64,9 @@ def accumulate_intensity(farplane, out=None):
         raise ValueError("out must have farplane's shape %s, got %s" % (shape, tuple(out.shape)))
     (g,), dev = _device(farplane)
     add = out is not None
+    _check_out(out, dev, "out must be a contiguous tensor on farplane's device")
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.device == dev):
-        raise ValueError("out must be a contiguous tensor on farplane's device")
     with torch.cuda.device(dev):
         nat.check(nat.fit_accumulate(_ptr(out), _ptr(g), g.numel(), int(add), _stream()))
     return out
@@ -99,8 +97,7 @@ def fit_frames(data, farplane=None, intensity=None, mask=None, ab=None, pixels=T
         frames = torch.empty((ptheta, nscan, 8), dtype=torch.float64, device=dev)
         maps = torch.empty((ptheta, 4, ndet, ndet), dtype=torch.float64, device=dev) if pixels else None
         work = torch.empty((max(words, 1),), dtype=torch.float64, device=dev)
-        opt = lambda t: None if t is None else _ptr(t)  # noqa: E731
-        nat.check(nat.fit_frames(_ptr(frames), opt(maps), opt(inten), opt(g), _ptr(d), opt(m), opt(ab_), ptheta, nscan,
+        nat.check(nat.fit_frames(_ptr(frames), _opt(maps), _opt(inten), _opt(g), _ptr(d), _opt(m), _opt(ab_), ptheta, nscan,
                                  npix, _ptr(work), _stream()))
     return {"frames": frames, "pixels": maps}
 

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from ._args import _device_of, _opt
 from .operators import PtychoHIP, _ptr, _stream
 from .registration import register_translation_batch
 
@@ -175,12 +176,7 @@ def ring_sums(a, b, region, taper, align):
     shape = tuple(a.shape)
     nz, n = shape[-2:]
     ptheta = shape[0] if len(shape) == 3 else 1
-    if isinstance(a, torch.Tensor) and a.is_cuda:
-        dev = a.device
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError("libtike.hipfft.frc needs a ROCm GPU; there is no CPU path")
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _device_of(a, "frc")
     K = s // 2 + 1
     with torch.cuda.device(dev):
         at, bt = _upload(a, dev, (ptheta, nz, n)), _upload(b, dev, (ptheta, nz, n))
@@ -188,8 +184,8 @@ def ring_sums(a, b, region, taper, align):
         win = None
         if taper > 0:
             win = torch.as_tensor(tukey_window(s, float(taper)).astype(np.float32), device=dev)
-        nat.check(nat.frc_prepare(_ptr(crops), _ptr(at), _ptr(bt), ptheta, nz, n, y0, x0, s,
-                                  None if win is None else _ptr(win), _stream()))
+        nat.check(nat.frc_prepare(_ptr(crops), _ptr(at), _ptr(bt), ptheta, nz, n, y0, x0, s, _opt(win),
+                                  _stream()))
         # a batch of one would meet the registration's "axis of length 1" rule (its shift is set to 0): register
         # every pair in a batch of at least two
         nb = max(ptheta, 2)

@@ -18,34 +18,12 @@ import numbers
 import torch
 
 from . import _native as nat
+from ._args import _array, _check_out, _device, _opt, _size
 from .operators import _ptr, _stream
 
 __all__ = ["illumination", "fit_gauge", "apply_gauge", "fix_gauge"]
 
 WHICH = {"object": 0, "probe": 1}
-
-
-def _dtype(x):
-    return str(getattr(x, "dtype", None)).replace("torch.", "")
-
-
-def _array(x, name, dtype, ranks):
-    """Shape of ``x`` after the dtype and rank checks (no device use)."""
-    if not hasattr(x, "shape") or not hasattr(x, "dtype"):
-        raise TypeError("%s must be an array, got %s" % (name, type(x).__name__))
-    if _dtype(x) != dtype:
-        raise TypeError("%s must be %s, got %s" % (name, dtype, _dtype(x)))
-    shape = tuple(int(v) for v in x.shape)
-    if len(shape) not in ranks or 0 in shape:
-        raise ValueError("%s must have %s non-empty axes, got shape %s"
-                         % (name, " or ".join(str(r) for r in ranks), shape))
-    return shape
-
-
-def _size(v, name):
-    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1:
-        raise ValueError("%s must be a positive integer, got %r" % (name, v))
-    return int(v)
 
 
 def check_illumination(scan, probe, nz, n, out=None):
@@ -99,20 +77,6 @@ def check_fix(psi, scan, probe, floor=0.1, ref=None):
     return ptheta, nz, n
 
 
-def _device(*tensors):
-    """Contiguous device tensors on one device (``None`` passes through); that device."""
-    dev = None
-    for t in tensors:
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError("libtike.hipfft works on device tensors; there is no CPU path")
-        if dev is not None and t.device != dev:
-            raise ValueError("operands live on different devices: %s and %s" % (dev, t.device))
-        dev = t.device
-    return [None if t is None else t.contiguous() for t in tensors], dev
-
-
 def illumination(scan, probe, nz, n, out=None):
     """The diagonal weight with which the object adjoint spreads ``|probe|^2`` over an ``nz x n`` object.
 
@@ -125,10 +89,9 @@ def illumination(scan, probe, nz, n, out=None):
     """
     ptheta, nscan, nmodes, nprb, nz, n = check_illumination(scan, probe, nz, n, out)
     (scan, probe), dev = _device(scan, probe)
+    _check_out(out, dev, "out must be a contiguous tensor on the operands' device")
     if out is None:
         out = torch.empty((ptheta, nz, n), dtype=torch.float32, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.device == dev):
-        raise ValueError("out must be a contiguous tensor on the operands' device")
     with torch.cuda.device(dev):
         nat.check(nat.illumination(_ptr(out), _ptr(scan), _ptr(probe), ptheta, nscan, nmodes, nprb, nz, n, _stream()))
     return out
@@ -150,8 +113,7 @@ def fit_gauge(psi, weight=None, ref=None):
     with torch.cuda.device(dev):
         gauge = torch.empty((ptheta, 6), dtype=torch.float64, device=dev)
         work = torch.empty((ptheta, nat.GAUGE_WORK_PER_ANGLE), dtype=torch.float64, device=dev)
-        nat.check(nat.gauge_fit(_ptr(gauge), _ptr(p), None if r is None else _ptr(r), None if w is None else _ptr(w),
-                                ptheta, nz, n, _ptr(work), _stream()))
+        nat.check(nat.gauge_fit(_ptr(gauge), _ptr(p), _opt(r), _opt(w), ptheta, nz, n, _ptr(work), _stream()))
     return gauge[0] if len(psi.shape) == 2 else gauge
 
 
@@ -166,8 +128,7 @@ def apply_gauge(x, gauge, which="object"):
     """
     ptheta, planes, ny, nx, code = check_apply(x, gauge, which)
     (g,), dev = _device(gauge)
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_contiguous() and x.device == dev):
-        raise ValueError("x must be a contiguous tensor on the gauge's device")
+    _check_out(x, dev, "x must be a contiguous tensor on the gauge's device")
     g = g.reshape(ptheta, 6)
     if planes > 1:
         g = g.repeat_interleave(planes, dim=0)     # one gauge row per probe mode

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .gauge import _array, _dtype
+from ._args import _check_out, _device_of, _dtype, _need_array, _opt
 from .operators import PtychoHIP, _ptr, _stream
 
 __all__ = ["prepare_frames", "initial_probe", "check_prepare"]
@@ -27,8 +27,7 @@ MAX_NDET = 32768
 def _plane(x, name, dtype, shape):
     if x is None:
         return
-    if not hasattr(x, "shape") or not hasattr(x, "dtype"):
-        raise TypeError("%s must be an array, got %s" % (name, type(x).__name__))
+    _need_array(x, name)
     if dtype is not None and _dtype(x) != dtype:
         raise TypeError("%s must be %s, got %s" % (name, dtype, _dtype(x)))
     if tuple(int(v) for v in x.shape) != shape:
@@ -42,8 +41,7 @@ def _contiguous(x):
 def check_prepare(raw, ndet, center=None, bin=1, dark=None, gain=None, bad=None, index=None, saturation=None, scale=1.0,
                   out=None):
     """Validate ``prepare_frames``'s arguments (no device use); returns ``(ptheta, nraw, nscan, H, W, y0, x0)``."""
-    if not hasattr(raw, "shape") or not hasattr(raw, "dtype"):
-        raise TypeError("raw must be an array, got %s" % type(raw).__name__)
+    _need_array(raw, "raw")
     if _dtype(raw) not in nat.PREPARE_DTYPES:
         raise TypeError("raw must be uint16, uint32, int32 or float32, got %s" % _dtype(raw))
     shape = tuple(int(v) for v in raw.shape)
@@ -70,8 +68,7 @@ def check_prepare(raw, ndet, center=None, bin=1, dark=None, gain=None, bad=None,
         _plane(x, name, dtype, (H, W))
     nscan = nraw
     if index is not None:
-        if not hasattr(index, "shape") or not hasattr(index, "dtype"):
-            raise TypeError("index must be an array, got %s" % type(index).__name__)
+        _need_array(index, "index")
         if _dtype(index) != "int64":
             raise TypeError("index must be int64, got %s" % _dtype(index))
         ishape = tuple(int(v) for v in index.shape)
@@ -135,11 +132,8 @@ def prepare_frames(raw, ndet, center=None, bin=1, dark=None, gain=None, bad=None
             raise ValueError("raw must be a device tensor or a NumPy array")
         dev = raw.device
     else:
-        if not torch.cuda.is_available():
-            raise RuntimeError("libtike.hipfft.prepare needs a ROCm GPU; there is no CPU path")
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.device == dev):
-        raise ValueError("out must be a contiguous tensor on raw's device")
+        dev = _device_of(None, "prepare")
+    _check_out(out, dev, "out must be a contiguous tensor on raw's device")
     code = nat.PREPARE_DTYPES[_dtype(raw)]
     npix = ndet * ndet
     words = int(nat.prepare_work_words(ptheta, nscan, npix))
@@ -152,9 +146,8 @@ def prepare_frames(raw, ndet, center=None, bin=1, dark=None, gain=None, bad=None
         frames = torch.empty((ptheta, nscan, 4), dtype=torch.float64, device=dev)
         maps = torch.empty((ptheta, 4, ndet, ndet), dtype=torch.float64, device=dev) if pixels else None
         work = torch.empty((max(words, 1),), dtype=torch.float64, device=dev)
-        opt = lambda t: None if t is None else _ptr(t)  # noqa: E731
-        nat.check(nat.prepare_frames(_ptr(data), _ptr(mask), _ptr(frames), opt(maps), _ptr(raw_d), code, opt(index_d),
-                                     opt(dark_d), opt(gain_d), opt(bad_d), ptheta, nraw, nscan, H, W, y0, x0, int(bin), ndet,
+        nat.check(nat.prepare_frames(_ptr(data), _ptr(mask), _ptr(frames), _opt(maps), _ptr(raw_d), code, _opt(index_d),
+                                     _opt(dark_d), _opt(gain_d), _opt(bad_d), ptheta, nraw, nscan, H, W, y0, x0, int(bin), ndet,
                                      float("nan") if saturation is None else float(saturation), float(scale),
                                      1 if clip else 0, _ptr(work), _stream()))
     return {"data": data, "mask": mask, "frames": frames, "pixels": maps}
@@ -170,8 +163,7 @@ def initial_probe(pattern, nprb, power=None):
     frame.  ``power``: rescale so that ``sum |probe|^2 == power`` per angle.  Returns complex64 ``[ptheta, 1, nprb,
     nprb]`` on the device.  Torch glue around the project's FFT on a temporary handle.
     """
-    if not hasattr(pattern, "shape") or not hasattr(pattern, "dtype"):
-        raise TypeError("pattern must be an array, got %s" % type(pattern).__name__)
+    _need_array(pattern, "pattern")
     shape = tuple(int(v) for v in pattern.shape)
     if len(shape) != 3 or 0 in shape or shape[-1] != shape[-2]:
         raise ValueError("pattern must be [ptheta, ndet, ndet], got shape %s" % (shape,))
@@ -182,12 +174,7 @@ def initial_probe(pattern, nprb, power=None):
         raise ValueError("nprb must be an integer in [1, ndet = %d], got %r" % (ndet, nprb))
     if power is not None and (isinstance(power, bool) or not isinstance(power, numbers.Real) or not power > 0):
         raise ValueError("power must be a positive number or None, got %r" % (power,))
-    if isinstance(pattern, torch.Tensor) and pattern.is_cuda:
-        dev = pattern.device
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError("libtike.hipfft.prepare needs a ROCm GPU; there is no CPU path")
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _device_of(pattern, "prepare")
     with torch.cuda.device(dev):
         pat = pattern if isinstance(pattern, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pattern))
         amp = torch.sqrt(torch.clamp(pat.to(dev).to(torch.float32), min=0.0)).to(torch.complex64).contiguous()

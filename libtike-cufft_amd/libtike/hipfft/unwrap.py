@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .gauge import _dtype
+from ._args import _check_out, _device_of, _dtype, _need_array, _opt
 from .operators import _ptr, _stream
 
 __all__ = ["unwrap_phase", "phase_residues", "check_unwrap"]
@@ -31,8 +31,7 @@ STATUS = {0: "running", 1: "converged", 2: "breakdown", 3: "maxiter"}
 
 
 def _shape(x, name, dtypes):
-    if not hasattr(x, "shape") or not hasattr(x, "dtype"):
-        raise TypeError("%s must be an array, got %s" % (name, type(x).__name__))
+    _need_array(x, name)
     if _dtype(x) not in dtypes:
         raise TypeError("%s must be %s, got %s" % (name, " or ".join(dtypes), _dtype(x)))
     return tuple(int(v) for v in x.shape)
@@ -75,9 +74,7 @@ def _on_device(x, weight):
                 raise ValueError("operands live on different devices: %s and %s" % (dev, t.device))
             dev = t.device
     if dev is None:
-        if not torch.cuda.is_available():
-            raise RuntimeError("libtike.hipfft.unwrap needs a ROCm GPU; there is no CPU path")
-        dev = torch.device("cuda", torch.cuda.current_device())
+        dev = _device_of(None, "unwrap")
 
     def move(t):
         return (t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t))).to(dev)
@@ -90,10 +87,6 @@ def _on_device(x, weight):
         if weight is not None:
             weight = move(weight).to(torch.float32).contiguous()
     return phase, weight, dev
-
-
-def _opt(t):
-    return None if t is None else _ptr(t)
 
 
 def unwrap_phase(x, weight=None, congruent=True, tol=1e-4, maxiter=None, check_every=256, out=None):
@@ -122,8 +115,7 @@ def unwrap_phase(x, weight=None, congruent=True, tol=1e-4, maxiter=None, check_e
     """
     ptheta, nz, n, maxiter = check_unwrap(x, weight, congruent, tol, maxiter, check_every, out)
     phase, w, dev = _on_device(x, weight)
-    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.device == dev):
-        raise ValueError("out must be a contiguous tensor on the operands' device")
+    _check_out(out, dev, "out must be a contiguous tensor on the operands' device")
     with torch.cuda.device(dev):
         buf = torch.empty((int(nat.unwrap_buffer_floats(ptheta, nz, n)),), dtype=torch.float32, device=dev)
         work = torch.empty((int(nat.unwrap_work_words(ptheta, nz, n)),), dtype=torch.float64, device=dev)
