@@ -90,10 +90,21 @@ int do_cg_adj_cols(ptycho_handle h, int slot, c32* f, const float* scan, c32* pr
     return rc;
 }
 
-// a fused row stage of a likelihood other than gaussian: the full-width variant where the launch covers the detector,
-// except for the projection (always the predicated one); nothing else is instantiated
-template <int N, int EP, bool MASK, int MODEL>
-void launch_rows_model(const RowFusedArgs& a, long long grid, hipStream_t st) {
+// The <FW, MASK, MODEL> variant of a fused row stage, one question at a time: MASK where the handle has a measured-pixel
+// mask and the stage reads data; the Poisson likelihood where it is set and the stage has variants of its own (PROJECT
+// and the line searches); FW where the launch covers the detector.  Every variant has the same launch shape, and none
+// but these is instantiated.
+// FW (unconditional masked loads): line search 0.292 -> 0.252 ms per pass, cross 1.65 -> 1.61, statistics 0.540 -> 0.517
+// (rocprofv3, 4096 x 256^2), projection 0.98 -> 1.01 -- it is always launched predicated and has no full-width variant;
+// 8.39 -> 8.33 ms per CG iteration by the wall clock
+template <int N, int EP, bool MASK = false, int MODEL = MODEL_GAUSSIAN>
+void launch_rows_fused(ptycho_handle h, const RowFusedArgs& a, long long grid, hipStream_t st) {
+    if constexpr (!MASK && EP != EP_CROSS) {
+        if (h->mask) return launch_rows_fused<N, EP, true, MODEL>(h, a, grid, st);
+    }
+    if constexpr (MODEL == MODEL_GAUSSIAN && (EP == EP_PROJECT || EP == EP_LINESEARCH || EP == EP_LINESEARCH_M)) {
+        if (h->model == MODEL_POISSON_ML) return launch_rows_fused<N, EP, MASK, MODEL_POISSON_ML>(h, a, grid, st);
+    }
     if constexpr (EP != EP_PROJECT) {
         if (a.xa == 0 && a.xb == N) {
             hipLaunchKernelGGL((k_rows_fused<N, EP, true, MASK, MODEL>), dim3((unsigned)grid), dim3(256), 0, st, a);
@@ -123,34 +134,10 @@ int do_cg_rows(ptycho_handle h, RowFusedArgs a, hipStream_t st) {
     }
     if (grid > h->fold_rows) grid = h->fold_rows;
     a.fold = h->fold;
+    a.mask = h->mask;   // read by the MASK variants only
     {
         ProfSpan ps(h, (EP == EP_STATS || EP == EP_STATS_M) ? K_ROWS_STATS : EP == EP_PROJECT ? K_ROWS_PROJECT : (EP == EP_LINESEARCH || EP == EP_LINESEARCH_M) ? K_ROWS_LINESEARCH : K_ROWS_CROSS, st);
-        // full-width variant (unconditional masked loads): line search 0.292 -> 0.252 ms per pass, cross 1.65 -> 1.61, statistics 0.540 -> 0.517
-        // (rocprofv3, 4096 x 256^2), projection 0.98 -> 1.01 (kept on the predicated variant); 8.39 -> 8.33 ms per CG iteration by the wall clock
-        if constexpr (EP == EP_PROJECT || EP == EP_LINESEARCH || EP == EP_LINESEARCH_M) {
-            if (h->model == MODEL_POISSON_ML) {   // Poisson likelihood: its own PROJECT / line-search variants (same launch shape)
-                a.mask = h->mask;
-                if (h->mask) launch_rows_model<N, EP, true, MODEL_POISSON_ML>(a, grid, st);
-                else launch_rows_model<N, EP, false, MODEL_POISSON_ML>(a, grid, st);
-                HIP_TRY(hipGetLastError());
-                return PTYCHO_OK;
-            }
-        }
-        if constexpr (EP != EP_CROSS) {
-            if (h->mask) {   // measured-pixel mask set: the MASK variants (same launch shape)
-                a.mask = h->mask;
-                if constexpr (EP != EP_PROJECT) {
-                    if (a.xa == 0 && a.xb == N) hipLaunchKernelGGL((k_rows_fused<N, EP, true, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
-                    else hipLaunchKernelGGL((k_rows_fused<N, EP, false, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
-                } else {
-                    hipLaunchKernelGGL((k_rows_fused<N, EP, false, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
-                }
-                HIP_TRY(hipGetLastError());
-                return PTYCHO_OK;
-            }
-        }
-        if (a.xa == 0 && a.xb == N && EP != EP_PROJECT) hipLaunchKernelGGL((k_rows_fused<N, EP, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_rows_fused<N, EP, false>), dim3((unsigned)grid), dim3(256), 0, st, a);
+        launch_rows_fused<N, EP>(h, a, grid, st);
     }
     HIP_TRY(hipGetLastError());
     return PTYCHO_OK;

@@ -36,6 +36,8 @@ __global__ __launch_bounds__(256) void k_lines_bluestein(const LineArgs a) {
     const int f = tid / T, j0 = tid % T;
     F fft;
     fft.init(j0, a.table);
+    auto put = [&](int i, c32 val) { lds[L::at(f, i)] = val; };   // the LDS row of this thread's transform
+    auto get = [&](int i) { return lds[L::at(f, i)]; };
     const c32 zero = c32{0.0f, 0.0f};
     const long long nb = (a.nlines + B - 1) / B;
     for (long long batch = blockIdx.x; batch < nb; batch += gridDim.x) {
@@ -53,21 +55,8 @@ __global__ __launch_bounds__(256) void k_lines_bluestein(const LineArgs a) {
             return DIR < 0 ? cmul(sl[(size_t)i * a.es], b) : cmulc(sl[(size_t)i * a.es], b);
         });
         // forward M-point FFT
-        fft.template compute<0>(v);
-        if (P::NSTEP > 1) {
-            fft.template store<0>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
-            __syncthreads();
-            fft.template load<1>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
-            if (P::NSTEP > 2) {
-                __syncthreads();
-                fft.template compute<1>(v);
-                fft.template store<1>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
-                __syncthreads();
-                fft.template load<2>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
-            }
-            fft.template compute<LAST>(v);
-            __syncthreads();
-        }
+        row_steps<true, false>(fft, v, j0, put, get);
+        if (P::NSTEP > 1) __syncthreads();
         F::to_natural(v, nat);
 #pragma unroll
         for (int m = 0; m < E; ++m) {
@@ -78,15 +67,15 @@ __global__ __launch_bounds__(256) void k_lines_bluestein(const LineArgs a) {
         F::from_natural(nat, v);
         fft.template compute_rev<0>(v);
         if (P::NSTEP > 1) {
-            fft.template store<0>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
+            fft.template store<0>(v, j0, put);
             __syncthreads();
-            fft.template load<1>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
+            fft.template load<1>(v, j0, get);
             if (P::NSTEP > 2) {
                 __syncthreads();
                 fft.template compute_rev<1>(v);
-                fft.template store<1>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
+                fft.template store<1>(v, j0, put);
                 __syncthreads();
-                fft.template load<2>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
+                fft.template load<2>(v, j0, get);
             }
             fft.template compute_rev<LAST>(v);
         }

@@ -3,6 +3,36 @@
 #pragma once
 
 // ---------------------------------------------------------------------------
+// One row transform in the plan's direction: every step on the row whose step-0 inputs sit in v; the outputs of the last
+// step are left in v (slot order).  The T threads of a row exchange through their own LDS row, which the caller hands
+// over as put(i, value) / get(i), and the caller synchronises once more before that row is written again.
+//   WGSYNC: a workgroup barrier between the steps whatever T is (row_sync)
+//   TWLDS:  each step re-reads its twiddles from wtab, an LDS copy of the table (Fft::init_step with the caller's opaque jz)
+// (The transforms against the plan's direction, and k_rows, stay written out: profiles/r13/rows_refactor_isa.txt.)
+// ---------------------------------------------------------------------------
+template <bool WGSYNC, bool TWLDS, class P, int DIR, class Put, class Get>
+__device__ __forceinline__ void row_steps(Fft<P, DIR>& fft, c32* v, const int j0, Put put, Get get, const int jz = 0,
+                                          const c32* wtab = nullptr) {
+    constexpr int T = P::T, LAST = P::NSTEP - 1;
+    fft.template compute<0>(v);
+    if constexpr (P::NSTEP > 1) {
+        fft.template store<0>(v, j0, put);
+        row_sync<T, WGSYNC>();
+        fft.template load<1>(v, j0, get);
+        if constexpr (P::NSTEP > 2) {
+            row_sync<T, WGSYNC>();
+            if constexpr (TWLDS) fft.template init_step<1>(jz, wtab);
+            fft.template compute<1>(v);
+            fft.template store<1>(v, j0, put);
+            row_sync<T, WGSYNC>();
+            fft.template load<2>(v, j0, get);
+        }
+        if constexpr (TWLDS) fft.template init_step<LAST>(jz, wtab);
+        fft.template compute<LAST>(v);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Row pass: DFT over x of contiguous rows, B = 256/T rows per workgroup step.
 // ---------------------------------------------------------------------------
 // (A full-width variant without the predicates below -- they put every request into a branch of its own -- was measured SLOWER by the
@@ -87,6 +117,8 @@ __global__ __launch_bounds__(256) void k_rows_split(const RowArgs a) {
     const int f = tid / T, j0 = tid % T;
     F fft;
     fft.init(j0, a.table);
+    auto put = [&](int i, c32 val) { lds[L::at(f, i)] = val; };   // the LDS row of this thread's transform
+    auto get = [&](int i) { return lds[L::at(f, i)]; };
     const c32 zero = c32{0.0f, 0.0f};
     const long long nitems = (a.nrows / N) * 16;
     for (long long item = blockIdx.x; item < nitems; item += gridDim.x) {
@@ -112,12 +144,8 @@ __global__ __launch_bounds__(256) void k_rows_split(const RowArgs a) {
             for (int t = 0; t < 16; ++t) lds[L::at(t, x)] = v[brev(t, 4)];
             __syncthreads();
             // ---- DFT over x of row f (final row jp + 16 f) ---------------------------------
-            fft.template load<0>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
-            fft.template compute<0>(v);
-            fft.template store<0>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
-            row_sync<T>();   // exchange inside row f: the row's 16 threads are lanes of one wave
-            fft.template load<1>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
-            fft.template compute<LAST>(v);
+            fft.template load<0>(v, j0, get);
+            row_steps<false, false>(fft, v, j0, put, get);   // exchange inside row f: the row's 16 threads are lanes of one wave
             c32* drow = dbase + (size_t)(jp + 16 * f) * N;
             fft.template store<LAST>(v, j0, [&](int i, c32 val) { __builtin_nontemporal_store(val, drow + i); });
             __syncthreads();
@@ -126,12 +154,12 @@ __global__ __launch_bounds__(256) void k_rows_split(const RowArgs a) {
             const c32* srow = sbase + (size_t)(jp + 16 * f) * N;
             fft.template load<0>(v, j0, [&](int i) { return __builtin_nontemporal_load(srow + i); });
             fft.template compute<0>(v);
-            fft.template store<0>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
+            fft.template store<0>(v, j0, put);
             row_sync<T>();
-            fft.template load<1>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
+            fft.template load<1>(v, j0, get);
             fft.template compute<LAST>(v);
             row_sync<T>();   // every exchange read of row f is done before the row is rewritten
-            fft.template store<LAST>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
+            fft.template store<LAST>(v, j0, put);
             __syncthreads();
             // ---- first radix-16 step of the IDFT over y, thread = column x -------------------
             const int x = tid;
@@ -184,6 +212,29 @@ __device__ __forceinline__ c32 pml_term(const c32 x, const c32 dl, const c32 c) 
     const c32 ax = c32{fabsf(x.x), fabsf(x.y)};
     return (ax - c) - dl * c32{flog2(ax.x + 1e-32f), flog2(ax.y + 1e-32f)};
 }
+// The line-search term of two detector pixels with data d as a function of their trial intensities x: gaussian
+// (sqrt|x| - sqrt d)^2, Poisson pml_term; what depends on d alone is formed once.  (The loop over the step lengths
+// stays with the two line searches: profiles/r13/rows_refactor_isa.txt.)
+template <bool PML>
+struct TrialTerm {
+    c32 sd, dl, c;   // gaussian: sqrt d; Poisson: d ln 2 and the pixel's constant (pml_shift)
+    __device__ __forceinline__ explicit TrialTerm(const c32 d) {
+        if constexpr (PML) {
+            dl = d * kLn2;
+            c = pml_shift(d, dl);
+        } else {
+            sd = c32{fsqrt(d.x), fsqrt(d.y)};
+        }
+    }
+    __device__ __forceinline__ c32 operator()(const c32 x) const {
+        if constexpr (PML) {
+            return pml_term(x, dl, c);
+        } else {
+            const c32 df = c32{fsqrt(fabsf(x.x)), fsqrt(fabsf(x.y))} - sd;
+            return df * df;
+        }
+    }
+};
 
 // An unconditional global load whose value is masked afterwards (m = all ones or zero, made opaque by the caller so that the
 // AND does not turn back into a select).  `pred ? load(p) : zero` puts every request into a branch of its own
@@ -404,25 +455,12 @@ __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(
         for (int i = blockIdx.x * 256 + tid; i < a.nbest; i += gridDim.x * 256) a.best_zero[i] = 0ull;
     }
 
+    auto put = [&](int i, c32 val) { lds[L::at(f, i)] = val; };   // the LDS row of this thread's transform
+    auto get = [&](int i) { return lds[L::at(f, i)]; };
     // forward DFT over x of one row held as step-0 inputs in v; result in natural order
     auto fwd_row = [&](c32* v, c32* nat) {
-        fft.template compute<0>(v);
-        if (P::NSTEP > 1) {
-            fft.template store<0>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
-            row_sync<T>();
-            fft.template load<1>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
-            if (P::NSTEP > 2) {
-                row_sync<T>();
-                if constexpr (TWLDS) fft.template init_step<1>(jz, wtab);
-                fft.template compute<1>(v);
-                fft.template store<1>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
-                row_sync<T>();
-                fft.template load<2>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
-            }
-            if constexpr (TWLDS) fft.template init_step<LAST>(jz, wtab);
-            fft.template compute<LAST>(v);
-            row_sync<T>();   // lds free for the next transform
-        }
+        row_steps<false, TWLDS>(fft, v, j0, put, get, jz, wtab);
+        if (P::NSTEP > 1) row_sync<T>();   // lds free for the next transform
         F::to_natural(v, nat);
     };
 
@@ -434,367 +472,329 @@ __global__ __launch_bounds__(256, (fused_min_waves<N, EP>())) void k_rows_fused(
     }
     const int nsweeps = multi ? 1 : ngroups;
     for (int grp = 0; grp < nsweeps; ++grp) {   // multi-mode line search: one sweep per group of 16 step lengths (else one pass)
-    const float gam_first = gamma0 * exp2f(-16.0f * (float)grp);
-    if (grp > 0) {
+        const float gam_first = gamma0 * exp2f(-16.0f * (float)grp);
+        if (grp > 0) {
 #pragma unroll
-        for (int i = 0; i < NACC; ++i) acc[i] = 0.0f;
+            for (int i = 0; i < NACC; ++i) acc[i] = 0.0f;
 #pragma unroll
-        for (int i = 0; i < (LS ? NACC : 1); ++i) acc2[i] = c32{0.0f, 0.0f};
-    }
-    for (long long batch = blockIdx.x; batch < nb; batch += gridDim.x) {
-        const long long r = batch * B + f;
-        const bool ok = r < a.nrows;
-        if constexpr (TWLDS) asm volatile("" : "+v"(jz));
-        // addresses = wave-uniform batch base (scalar registers) + 32-bit per-thread offset: the
-        // loads / stores take the saddr form and no 64-bit address lives in a VGPR
-        const size_t boff = (size_t)batch * B * N;
-        const unsigned fN = (unsigned)(f * N);
-        const unsigned fNs = ok ? fN : 0u;   // FW: a row past the end reads row 0 of its batch (always there) ...
-        unsigned rowm = ok ? 0xffffffffu : 0u;   // ... and masks it
-        if constexpr (FW) asm volatile("" : "+v"(rowm));
-        c32 v[E], g1[E];
-        const c32* __restrict__ first_src = (EP == EP_LINESEARCH_M || EP == EP_STATS_M) ? a.sm[0] : a.s1;
-        auto request = [&](const c32* __restrict__ src, c32* dstv) {
-            fft.template load<0>(dstv, j0, [&](int i) { if constexpr (FW) return load_masked(src + boff + (fNs + (unsigned)i), rowm); else return (ok && i >= a.xa && i < a.xb) ? __builtin_nontemporal_load(src + boff + (fN + (unsigned)i)) : zero; });
-        };
-        request(first_src, v);
-        // (Round 4 tried requesting the 2 nmodes input rows of the multi-mode line search one transform AHEAD, ping-pong between two
-        // register sets: 124.8 -> 125.6-126.2 ms per configs[2] iteration -- the kernel is not waiting on its loads (SQ counters: VALU
-        // active 47 % of the SIMD cycles, issue stalls 24 %, waits 30 %); a first form that copied the prefetched row and kept the
-        // masked loads exploded to 581-1116 spilled registers and 441 ms.  profiles/r04/cfg3_experiments.txt.)
-        fwd_row(v, g1);
-        float d[E];
-        unsigned mw = 0u;   // MASK: this thread's measured-pixel word of row r % N (read in load_data)
-        auto load_data = [&]() {
-            if constexpr (MASK) mw = a.mask[(unsigned)(r % N) * T + j0];
-#pragma unroll
-            for (int m = 0; m < E; ++m) {
-                if constexpr (FW) d[m] = load_masked(a.data + boff + (fNs + (unsigned)(j0 + m * T)), rowm);
-                else d[m] = ok ? __builtin_nontemporal_load(a.data + boff + (fN + (unsigned)(j0 + m * T))) : 0.0f;
-                if constexpr (MASK) d[m] = and_f(d[m], mask_bit(mw, m));
-            }
-        };
-        if (EP == EP_STATS || EP == EP_PROJECT) load_data();
-        if (EP == EP_CROSS) {
-            // position correction (ptycho.py:398-403,198-204): u1 = G psi, u2 = G(psi + gamma dpsi)
-            // = u1 + gamma G dpsi (ones probe); image product u1 conj(u2) is kept for the zoomed
-            // DFT and its inverse row DFT goes back into the slot (column pass + arg-max follow).
-            c32 g2[E], rr[E];
-            // u1 waits in LDS (private slots, no barrier) while the second row is transformed: the
-            // kernel then fits 256 VGPRs and two waves per SIMD instead of one
-#pragma unroll
-            for (int m = 0; m < E; ++m) stash[m * 256 + tid] = g1[m];
-            fft.template load<0>(v, j0, [&](int i) { if constexpr (FW) return load_masked(a.s2 + boff + (fNs + (unsigned)i), rowm); else return (ok && i >= a.xa && i < a.xb) ? __builtin_nontemporal_load(a.s2 + boff + (fN + (unsigned)i)) : zero; });
-            fwd_row(v, g2);
-#pragma unroll
-            for (int m = 0; m < E; ++m) g1[m] = stash[m * 256 + tid];
-#pragma unroll
-            for (int m = 0; m < E; ++m) {
-                const c32 u2 = g1[m] + g2[m] * gamma0;
-                rr[m] = cmulc(g1[m], u2);
-                if (ok) __builtin_nontemporal_store(rr[m], a.ip + boff + (fN + (unsigned)(j0 + m * T)));
-            }
-            F::from_natural(rr, v);
-            fft.template compute_rev<0>(v);
-            if (P::NSTEP > 1) {
-                fft.template store<0>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
-                row_sync<T>();
-                fft.template load<1>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
-                if (P::NSTEP > 2) {
-                    row_sync<T>();
-                    if constexpr (TWLDS) fft.template init_step<1>(jz, wtab);
-                    fft.template compute_rev<1>(v);
-                    fft.template store<1>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
-                    row_sync<T>();
-                    fft.template load<2>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
-                }
-                if constexpr (TWLDS) fft.template init_step<LAST>(jz, wtab);
-                fft.template compute_rev<LAST>(v);
-            }
-            fft.template store<LAST>(v, j0, [&](int i, c32 val) {
-                if (ok) __builtin_nontemporal_store(val, a.out + boff + (fN + (unsigned)i));
-            });
-            if (P::NSTEP > 1) row_sync<T>();
-            continue;
+            for (int i = 0; i < (LS ? NACC : 1); ++i) acc2[i] = c32{0.0f, 0.0f};
         }
-
-        if (EP == EP_STATS) {
-#pragma unroll
-            for (int m = 0; m < E; ++m) {
-                float I = g1[m].x * g1[m].x + g1[m].y * g1[m].y;
-                if constexpr (MASK) I = and_f(I, mask_bit(mw, m));
-                acc[0] += fsqrt(I * d[m]);
-                acc[1] += I;
-            }
-        } else if (EP == EP_STATS_M) {
-            // summed intensity of nmodes slots sm[0..nmodes) (ptycho.py:329-333): written to acc1 if
-            // given, and the statistics of :342-343 added to sums if given -- one pass instead of
-            // one accumulate pass per mode plus an array reduction
-            float I[E];
-#pragma unroll
-            for (int m = 0; m < E; ++m) I[m] = g1[m].x * g1[m].x + g1[m].y * g1[m].y;
-            for (int k = 1; k < a.nmodes; ++k) {
-                const c32* __restrict__ src = a.sm[k];
-                fft.template load<0>(v, j0, [&](int i) { if constexpr (FW) return load_masked(src + boff + (fNs + (unsigned)i), rowm); else return (ok && i >= a.xa && i < a.xb) ? __builtin_nontemporal_load(src + boff + (fN + (unsigned)i)) : zero; });
-                fwd_row(v, g1);
-#pragma unroll
-                for (int m = 0; m < E; ++m) I[m] += g1[m].x * g1[m].x + g1[m].y * g1[m].y;
-            }
-            if (a.acc1 && ok) {
-#pragma unroll
-                for (int m = 0; m < E; ++m) a.acc1[boff + (fN + (unsigned)(j0 + m * T))] = I[m];
-            }
-            if (a.sums) {
-                load_data();
+        for (long long batch = blockIdx.x; batch < nb; batch += gridDim.x) {
+            const long long r = batch * B + f;
+            const bool ok = r < a.nrows;
+            if constexpr (TWLDS) asm volatile("" : "+v"(jz));
+            // addresses = wave-uniform batch base (scalar registers) + 32-bit per-thread offset: the
+            // loads / stores take the saddr form and no 64-bit address lives in a VGPR
+            const size_t boff = (size_t)batch * B * N;
+            const unsigned fN = (unsigned)(f * N);
+            const unsigned fNs = ok ? fN : 0u;   // FW: a row past the end reads row 0 of its batch (always there) ...
+            unsigned rowm = ok ? 0xffffffffu : 0u;   // ... and masks it
+            if constexpr (FW) asm volatile("" : "+v"(rowm));
+            c32 v[E], g1[E];
+            const c32* __restrict__ first_src = (EP == EP_LINESEARCH_M || EP == EP_STATS_M) ? a.sm[0] : a.s1;
+            auto request = [&](const c32* __restrict__ src, c32* dstv) {
+                fft.template load<0>(dstv, j0, [&](int i) { if constexpr (FW) return load_masked(src + boff + (fNs + (unsigned)i), rowm); else return (ok && i >= a.xa && i < a.xb) ? __builtin_nontemporal_load(src + boff + (fN + (unsigned)i)) : zero; });
+            };
+            request(first_src, v);
+            // (Round 4 tried requesting the 2 nmodes input rows of the multi-mode line search one transform AHEAD, ping-pong between two
+            // register sets: 124.8 -> 125.6-126.2 ms per configs[2] iteration -- the kernel is not waiting on its loads (SQ counters: VALU
+            // active 47 % of the SIMD cycles, issue stalls 24 %, waits 30 %); a first form that copied the prefetched row and kept the
+            // masked loads exploded to 581-1116 spilled registers and 441 ms.  profiles/r04/cfg3_experiments.txt.)
+            fwd_row(v, g1);
+            float d[E];
+            unsigned mw = 0u;   // MASK: this thread's measured-pixel word of row r % N (read in load_data)
+            auto load_data = [&]() {
+                if constexpr (MASK) mw = a.mask[(unsigned)(r % N) * T + j0];
 #pragma unroll
                 for (int m = 0; m < E; ++m) {
-                    if constexpr (MASK) I[m] = and_f(I[m], mask_bit(mw, m));
-                    acc[0] += fsqrt(I[m] * d[m]);
-                    acc[1] += I[m];
+                    if constexpr (FW) d[m] = load_masked(a.data + boff + (fNs + (unsigned)(j0 + m * T)), rowm);
+                    else d[m] = ok ? __builtin_nontemporal_load(a.data + boff + (fN + (unsigned)(j0 + m * T))) : 0.0f;
+                    if constexpr (MASK) d[m] = and_f(d[m], mask_bit(mw, m));
                 }
-            }
-        } else if (EP == EP_PROJECT) {
-            const float s2 = s * s;
-            c32 rr[E];
+            };
+            if (EP == EP_STATS || EP == EP_PROJECT) load_data();
+            if (EP == EP_CROSS) {
+                // position correction (ptycho.py:398-403,198-204): u1 = G psi, u2 = G(psi + gamma dpsi)
+                // = u1 + gamma G dpsi (ones probe); image product u1 conj(u2) is kept for the zoomed
+                // DFT and its inverse row DFT goes back into the slot (column pass + arg-max follow).
+                c32 g2[E], rr[E];
+                // u1 waits in LDS (private slots, no barrier) while the second row is transformed: the
+                // kernel then fits 256 VGPRs and two waves per SIMD instead of one
 #pragma unroll
-            for (int m = 0; m < E; ++m) {
-                // single mode: S comes from the unscaled probe -> I' = |g|^2 s^2, fpsi = (g s)(1/s');
-                // multi mode: S comes from the rescaled probe and I is the summed intensity array
-                float I = a.inten ? (ok ? a.inten[boff + (fN + (unsigned)(j0 + m * T))] : 0.0f) * s2
-                                  : (g1[m].x * g1[m].x + g1[m].y * g1[m].y) * s2;
-                if constexpr (MASK) I = and_f(I, mask_bit(mw, m));
-                const c32 fp = (a.inten && !a.first) ? g1[m] * sinv : (g1[m] * s) * sinv;
-                if constexpr (PML) {
-                    // unbounded where I' -> 0 with d > 0 (|r| up to ~d / (2 sqrt(1e-32))): maxword below is the max of
-                    // the row actually stored, so the deterministic adjoint's fixed point follows it
-                    rr[m] = fp - (fp * d[m]) * frcp(I + 1e-32f);
-                    if constexpr (MASK) rr[m] = and_c(rr[m], mask_bit(mw, m));
-                    acc[0] += ok ? I - (d[m] * kLn2) * flog2(I + 1e-32f) : 0.0f;
-                } else {
-                    const float sd = fsqrt(d[m]), sI = fsqrt(I);
-                    rr[m] = fp - (fp * sd) * frcp(sI + 1e-32f);
-                    if constexpr (MASK) rr[m] = and_c(rr[m], mask_bit(mw, m));
-                    const float df = sI - sd;
-                    acc[0] += ok ? df * df : 0.0f;
-                }
-            }
-            // inverse DFT over x of the projected row, same twiddle registers (conjugated)
-            F::from_natural(rr, v);
-            fft.template compute_rev<0>(v);
-            if (P::NSTEP > 1) {
-                fft.template store<0>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
-                row_sync<T>();
-                fft.template load<1>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
-                if (P::NSTEP > 2) {
-                    row_sync<T>();
-                    if constexpr (TWLDS) fft.template init_step<1>(jz, wtab);
-                    fft.template compute_rev<1>(v);
-                    fft.template store<1>(v, j0, [&](int i, c32 val) { lds[L::at(f, i)] = val; });
-                    row_sync<T>();
-                    fft.template load<2>(v, j0, [&](int i) { return lds[L::at(f, i)]; });
-                }
-                if constexpr (TWLDS) fft.template init_step<LAST>(jz, wtab);
-                fft.template compute_rev<LAST>(v);
-            }
-            if (a.maxword && ok) {
-#pragma unroll
-                for (int m = 0; m < E; ++m) vmax2 = fmaxf(vmax2, v[m].x * v[m].x + v[m].y * v[m].y);
-            }
-            fft.template store<LAST>(v, j0, [&](int i, c32 val) {
-                if (ok) __builtin_nontemporal_store(val, a.out + boff + (fN + (unsigned)i));
-            });
-            if (P::NSTEP > 1) row_sync<T>();
-        } else if (EP == EP_LINESEARCH_M) {
-            // multi-mode line search (ptycho.py:383-393 with the sums over k of :386-391): the terms
-            // p1, p2, p3 are accumulated over the modes in registers, never stored
-            float p1[E], p2[E], p3[E];
-#pragma unroll
-            for (int m = 0; m < E; ++m) { p1[m] = 0.0f; p2[m] = 0.0f; p3[m] = 0.0f; }
-            for (int k = 0; k < a.nmodes; ++k) {
-                if (k > 0) {
-                    request(a.sm[2 * k], v);
-                    fwd_row(v, g1);
-                }
-#pragma unroll
-                for (int m = 0; m < E; ++m) stash[m * 256 + tid] = g1[m];   // t1 waits in LDS (private slots)
-                c32 g2[E];
-                request(a.sm[2 * k + 1], v);
+                for (int m = 0; m < E; ++m) stash[m * 256 + tid] = g1[m];
+                request(a.s2, v);
                 fwd_row(v, g2);
 #pragma unroll
-                for (int m = 0; m < E; ++m) {
-                    const c32 t1 = stash[m * 256 + tid] * s;
-                    p1[m] += t1.x * t1.x + t1.y * t1.y;
-                    p2[m] += g2[m].x * g2[m].x + g2[m].y * g2[m].y;
-                    p3[m] += 2.0f * (t1.x * g2[m].x + t1.y * g2[m].y);
-                }
-            }
-            load_data();
-            if (a.inten) {
-#pragma unroll
-                for (int m = 0; m < E; ++m) p1[m] = ok ? a.inten[boff + (fN + (unsigned)(j0 + m * T))] : 0.0f;
-            }
-            if constexpr (MASK) {
+                for (int m = 0; m < E; ++m) g1[m] = stash[m * 256 + tid];
 #pragma unroll
                 for (int m = 0; m < E; ++m) {
-                    const unsigned mb = mask_bit(mw, m);
-                    p1[m] = and_f(p1[m], mb); p2[m] = and_f(p2[m], mb); p3[m] = and_f(p3[m], mb);
+                    const c32 u2 = g1[m] + g2[m] * gamma0;
+                    rr[m] = cmulc(g1[m], u2);
+                    if (ok) __builtin_nontemporal_store(rr[m], a.ip + boff + (fN + (unsigned)(j0 + m * T)));
                 }
+                F::from_natural(rr, v);
+                fft.template compute_rev<0>(v);
+                if (P::NSTEP > 1) {
+                    fft.template store<0>(v, j0, put);
+                    row_sync<T>();
+                    fft.template load<1>(v, j0, get);
+                    if (P::NSTEP > 2) {
+                        row_sync<T>();
+                        if constexpr (TWLDS) fft.template init_step<1>(jz, wtab);
+                        fft.template compute_rev<1>(v);
+                        fft.template store<1>(v, j0, put);
+                        row_sync<T>();
+                        fft.template load<2>(v, j0, get);
+                    }
+                    if constexpr (TWLDS) fft.template init_step<LAST>(jz, wtab);
+                    fft.template compute_rev<LAST>(v);
+                }
+                fft.template store<LAST>(v, j0, [&](int i, c32 val) {
+                    if (ok) __builtin_nontemporal_store(val, a.out + boff + (fN + (unsigned)i));
+                });
+                if (P::NSTEP > 1) row_sync<T>();
+                continue;
             }
+
+            if (EP == EP_STATS) {
 #pragma unroll
-            for (int m = 0; m < E; m += 2) {
-                const c32 q1 = c32{p1[m], p1[m + 1]}, q2 = c32{p2[m], p2[m + 1]}, q3 = c32{p3[m], p3[m + 1]};
-                if constexpr (PML) {
-                    const c32 dd = c32{d[m], d[m + 1]}, dl = dd * kLn2, c = pml_shift(dd, dl);
-                    acc2[kMaxCand] += pml_term(q1, dl, c);
+                for (int m = 0; m < E; ++m) {
+                    float I = g1[m].x * g1[m].x + g1[m].y * g1[m].y;
+                    if constexpr (MASK) I = and_f(I, mask_bit(mw, m));
+                    acc[0] += fsqrt(I * d[m]);
+                    acc[1] += I;
+                }
+            } else if (EP == EP_STATS_M) {
+                // summed intensity of nmodes slots sm[0..nmodes) (ptycho.py:329-333): written to acc1 if
+                // given, and the statistics of :342-343 added to sums if given -- one pass instead of
+                // one accumulate pass per mode plus an array reduction
+                float I[E];
+#pragma unroll
+                for (int m = 0; m < E; ++m) I[m] = g1[m].x * g1[m].x + g1[m].y * g1[m].y;
+                for (int k = 1; k < a.nmodes; ++k) {
+                    request(a.sm[k], v);
+                    fwd_row(v, g1);
+#pragma unroll
+                    for (int m = 0; m < E; ++m) I[m] += g1[m].x * g1[m].x + g1[m].y * g1[m].y;
+                }
+                if (a.acc1 && ok) {
+#pragma unroll
+                    for (int m = 0; m < E; ++m) a.acc1[boff + (fN + (unsigned)(j0 + m * T))] = I[m];
+                }
+                if (a.sums) {
+                    load_data();
+#pragma unroll
+                    for (int m = 0; m < E; ++m) {
+                        if constexpr (MASK) I[m] = and_f(I[m], mask_bit(mw, m));
+                        acc[0] += fsqrt(I[m] * d[m]);
+                        acc[1] += I[m];
+                    }
+                }
+            } else if (EP == EP_PROJECT) {
+                const float s2 = s * s;
+                c32 rr[E];
+#pragma unroll
+                for (int m = 0; m < E; ++m) {
+                    // single mode: S comes from the unscaled probe -> I' = |g|^2 s^2, fpsi = (g s)(1/s');
+                    // multi mode: S comes from the rescaled probe and I is the summed intensity array
+                    float I = a.inten ? (ok ? a.inten[boff + (fN + (unsigned)(j0 + m * T))] : 0.0f) * s2
+                                      : (g1[m].x * g1[m].x + g1[m].y * g1[m].y) * s2;
+                    if constexpr (MASK) I = and_f(I, mask_bit(mw, m));
+                    const c32 fp = (a.inten && !a.first) ? g1[m] * sinv : (g1[m] * s) * sinv;
+                    if constexpr (PML) {
+                        // unbounded where I' -> 0 with d > 0 (|r| up to ~d / (2 sqrt(1e-32))): maxword below is the max of
+                        // the row actually stored, so the deterministic adjoint's fixed point follows it
+                        rr[m] = fp - (fp * d[m]) * frcp(I + 1e-32f);
+                        if constexpr (MASK) rr[m] = and_c(rr[m], mask_bit(mw, m));
+                        acc[0] += ok ? I - (d[m] * kLn2) * flog2(I + 1e-32f) : 0.0f;
+                    } else {
+                        const float sd = fsqrt(d[m]), sI = fsqrt(I);
+                        rr[m] = fp - (fp * sd) * frcp(sI + 1e-32f);
+                        if constexpr (MASK) rr[m] = and_c(rr[m], mask_bit(mw, m));
+                        const float df = sI - sd;
+                        acc[0] += ok ? df * df : 0.0f;
+                    }
+                }
+                // inverse DFT over x of the projected row, same twiddle registers (conjugated)
+                F::from_natural(rr, v);
+                fft.template compute_rev<0>(v);
+                if (P::NSTEP > 1) {
+                    fft.template store<0>(v, j0, put);
+                    row_sync<T>();
+                    fft.template load<1>(v, j0, get);
+                    if (P::NSTEP > 2) {
+                        row_sync<T>();
+                        if constexpr (TWLDS) fft.template init_step<1>(jz, wtab);
+                        fft.template compute_rev<1>(v);
+                        fft.template store<1>(v, j0, put);
+                        row_sync<T>();
+                        fft.template load<2>(v, j0, get);
+                    }
+                    if constexpr (TWLDS) fft.template init_step<LAST>(jz, wtab);
+                    fft.template compute_rev<LAST>(v);
+                }
+                if (a.maxword && ok) {
+#pragma unroll
+                    for (int m = 0; m < E; ++m) vmax2 = fmaxf(vmax2, v[m].x * v[m].x + v[m].y * v[m].y);
+                }
+                fft.template store<LAST>(v, j0, [&](int i, c32 val) {
+                    if (ok) __builtin_nontemporal_store(val, a.out + boff + (fN + (unsigned)i));
+                });
+                if (P::NSTEP > 1) row_sync<T>();
+            } else if (EP == EP_LINESEARCH_M) {
+                // multi-mode line search (ptycho.py:383-393 with the sums over k of :386-391): the terms
+                // p1, p2, p3 are accumulated over the modes in registers, never stored
+                float p1[E], p2[E], p3[E];
+#pragma unroll
+                for (int m = 0; m < E; ++m) { p1[m] = 0.0f; p2[m] = 0.0f; p3[m] = 0.0f; }
+                for (int k = 0; k < a.nmodes; ++k) {
+                    if (k > 0) {
+                        request(a.sm[2 * k], v);
+                        fwd_row(v, g1);
+                    }
+#pragma unroll
+                    for (int m = 0; m < E; ++m) stash[m * 256 + tid] = g1[m];   // t1 waits in LDS (private slots)
+                    c32 g2[E];
+                    request(a.sm[2 * k + 1], v);
+                    fwd_row(v, g2);
+#pragma unroll
+                    for (int m = 0; m < E; ++m) {
+                        const c32 t1 = stash[m * 256 + tid] * s;
+                        p1[m] += t1.x * t1.x + t1.y * t1.y;
+                        p2[m] += g2[m].x * g2[m].x + g2[m].y * g2[m].y;
+                        p3[m] += 2.0f * (t1.x * g2[m].x + t1.y * g2[m].y);
+                    }
+                }
+                load_data();
+                if (a.inten) {
+#pragma unroll
+                    for (int m = 0; m < E; ++m) p1[m] = ok ? a.inten[boff + (fN + (unsigned)(j0 + m * T))] : 0.0f;
+                }
+                if constexpr (MASK) {
+#pragma unroll
+                    for (int m = 0; m < E; ++m) {
+                        const unsigned mb = mask_bit(mw, m);
+                        p1[m] = and_f(p1[m], mb); p2[m] = and_f(p2[m], mb); p3[m] = and_f(p3[m], mb);
+                    }
+                }
+#pragma unroll
+                for (int m = 0; m < E; m += 2) {
+                    const c32 q1 = c32{p1[m], p1[m + 1]}, q2 = c32{p2[m], p2[m + 1]}, q3 = c32{p3[m], p3[m + 1]};
+                    const TrialTerm<PML> term(c32{d[m], d[m + 1]});
+                    acc2[kMaxCand] += term(q1);
                     float gam = gam_first;
 #pragma unroll
-                    for (int j0c = 0; j0c < kMaxCand; j0c += 4) {
+                    for (int j0c = 0; j0c < kMaxCand; j0c += 4) {   // four step lengths per uniform branch
                         if (j0c < ncand) {
 #pragma unroll
                             for (int j = j0c; j < j0c + 4; ++j) {
-                                acc2[j] += pml_term(q1 + q2 * (gam * gam) + q3 * gam, dl, c);
+                                acc2[j] += term(q1 + q2 * (gam * gam) + q3 * gam);
                                 gam *= 0.5f;
                             }
                         }
                     }
-                    continue;
                 }
-                const c32 sd = c32{fsqrt(d[m]), fsqrt(d[m + 1])};
-                c32 df = c32{fsqrt(fabsf(q1.x)), fsqrt(fabsf(q1.y))} - sd;
-                acc2[kMaxCand] += df * df;
-                float gam = gam_first;
+            } else {   // EP_LINESEARCH
+                c32 g2[E];
+                // written out, not request(a.s2, v): through the lambda the predicated ndet 256 kernels get another order of register moves
+                fft.template load<0>(v, j0, [&](int i) { if constexpr (FW) return load_masked(a.s2 + boff + (fNs + (unsigned)i), rowm); else return (ok && i >= a.xa && i < a.xb) ? __builtin_nontemporal_load(a.s2 + boff + (fN + (unsigned)i)) : zero; });
+                fwd_row(v, g2);
+                load_data();   // after the second transform: keeps 16 registers free during it
+                // two detector pixels per step in packed float32 (v_pk_fma_f32 / v_pk_add_f32), four
+                // step lengths per uniform branch: per trial and pixel 2 FMA for p1 + y^2 p2 + y p3,
+                // one v_sqrt_f32, one subtract, one FMA into the cost
+                const int ginner = multi ? ngroups : 1;
+                for (int gi = 0; gi < ginner; ++gi) {
+                    const float gfirst = multi ? gamma0 * exp2f(-16.0f * (float)gi) : gam_first;
+                    if (multi) {
 #pragma unroll
-                for (int j0c = 0; j0c < kMaxCand; j0c += 4) {
-                    if (j0c < ncand) {
-#pragma unroll
-                        for (int j = j0c; j < j0c + 4; ++j) {
-                            const c32 xx = q1 + q2 * (gam * gam) + q3 * gam;
-                            df = c32{fsqrt(fabsf(xx.x)), fsqrt(fabsf(xx.y))} - sd;
-                            acc2[j] += df * df;
-                            gam *= 0.5f;
-                        }
+                        for (int i = 0; i < NACC; ++i) acc2[i] = c32{0.0f, 0.0f};
                     }
-                }
-            }
-        } else {   // EP_LINESEARCH
-            c32 g2[E];
-            fft.template load<0>(v, j0, [&](int i) { if constexpr (FW) return load_masked(a.s2 + boff + (fNs + (unsigned)i), rowm); else return (ok && i >= a.xa && i < a.xb) ? __builtin_nontemporal_load(a.s2 + boff + (fN + (unsigned)i)) : zero; });
-            fwd_row(v, g2);
-            load_data();   // after the second transform: keeps 16 registers free during it
-            // two detector pixels per step in packed float32 (v_pk_fma_f32 / v_pk_add_f32), four
-            // step lengths per uniform branch: per trial and pixel 2 FMA for p1 + y^2 p2 + y p3,
-            // one v_sqrt_f32, one subtract, one FMA into the cost
-            const int ginner = multi ? ngroups : 1;
-            for (int gi = 0; gi < ginner; ++gi) {
-            const float gfirst = multi ? gamma0 * exp2f(-16.0f * (float)gi) : gam_first;
-            if (multi) {
 #pragma unroll
-                for (int i = 0; i < NACC; ++i) acc2[i] = c32{0.0f, 0.0f};
-            }
+                    for (int m = 0; m < E; m += 2) {
+                        c32 ta = g1[m] * s, tb = g1[m + 1] * s, ua = g2[m], ub = g2[m + 1];
+                        if constexpr (MASK) {   // t1 = s g1, t2 = g2 of an unmeasured pixel are 0: p1 = p2 = p3 = 0 exactly
+                            const unsigned ma = mask_bit(mw, m), mb = mask_bit(mw, m + 1);
+                            ta = and_c(ta, ma); ua = and_c(ua, ma); tb = and_c(tb, mb); ub = and_c(ub, mb);
+                        }
+                        const c32 p1 = c32{ta.x * ta.x + ta.y * ta.y, tb.x * tb.x + tb.y * tb.y};
+                        const c32 p2 = c32{ua.x * ua.x + ua.y * ua.y, ub.x * ub.x + ub.y * ub.y};
+                        const c32 p3 = c32{2.0f * (ta.x * ua.x + ta.y * ua.y), 2.0f * (tb.x * ub.x + tb.y * ub.y)};
+                        const TrialTerm<PML> term(c32{d[m], d[m + 1]});
+                        acc2[kMaxCand] += term(p1);
+                        float gam = gfirst;
 #pragma unroll
-            for (int m = 0; m < E; m += 2) {
-                c32 ta = g1[m] * s, tb = g1[m + 1] * s, ua = g2[m], ub = g2[m + 1];
-                if constexpr (MASK) {   // t1 = s g1, t2 = g2 of an unmeasured pixel are 0: p1 = p2 = p3 = 0 exactly
-                    const unsigned ma = mask_bit(mw, m), mb = mask_bit(mw, m + 1);
-                    ta = and_c(ta, ma); ua = and_c(ua, ma); tb = and_c(tb, mb); ub = and_c(ub, mb);
-                }
-                const c32 p1 = c32{ta.x * ta.x + ta.y * ta.y, tb.x * tb.x + tb.y * tb.y};
-                const c32 p2 = c32{ua.x * ua.x + ua.y * ua.y, ub.x * ub.x + ub.y * ub.y};
-                const c32 p3 = c32{2.0f * (ta.x * ua.x + ta.y * ua.y), 2.0f * (tb.x * ub.x + tb.y * ub.y)};
-                if constexpr (PML) {
-                    const c32 dd = c32{d[m], d[m + 1]}, dl = dd * kLn2, c = pml_shift(dd, dl);
-                    acc2[kMaxCand] += pml_term(p1, dl, c);
-                    float gam = gfirst;
+                        for (int j0c = 0; j0c < kMaxCand; j0c += 4) {
+                            if (j0c < ncand) {
 #pragma unroll
-                    for (int j0c = 0; j0c < kMaxCand; j0c += 4) {
-                        if (j0c < ncand) {
-#pragma unroll
-                            for (int j = j0c; j < j0c + 4; ++j) {
-                                acc2[j] += pml_term(p1 + p2 * (gam * gam) + p3 * gam, dl, c);
-                                gam *= 0.5f;
+                                for (int j = j0c; j < j0c + 4; ++j) {
+                                    acc2[j] += term(p1 + p2 * (gam * gam) + p3 * gam);
+                                    gam *= 0.5f;
+                                }
                             }
                         }
                     }
-                    continue;
-                }
-                const c32 sd = c32{fsqrt(d[m]), fsqrt(d[m + 1])};
-                c32 df = c32{fsqrt(fabsf(p1.x)), fsqrt(fabsf(p1.y))} - sd;
-                acc2[kMaxCand] += df * df;
-                float gam = gfirst;
+                    if (multi) {
+                        // wave reduction of the 16 + 1 partial costs: halve the values per lane at every exchange (15 + 2
+                        // shuffles for the 16, 6 for f(p1)); lane l < 16 ends up with the wave total of value brev4(l)
+                        const int lane = tid & 63, wave = tid >> 6;
+                        float r[kMaxCand];
 #pragma unroll
-                for (int j0c = 0; j0c < kMaxCand; j0c += 4) {
-                    if (j0c < ncand) {
+                        for (int i = 0; i < kMaxCand; ++i) r[i] = acc2[i].x + acc2[i].y;
+                        float x16 = acc2[kMaxCand].x + acc2[kMaxCand].y;
 #pragma unroll
-                        for (int j = j0c; j < j0c + 4; ++j) {
-                            const c32 xx = p1 + p2 * (gam * gam) + p3 * gam;
-                            df = c32{fsqrt(fabsf(xx.x)), fsqrt(fabsf(xx.y))} - sd;
-                            acc2[j] += df * df;
-                            gam *= 0.5f;
-                        }
+                        for (int i = 0; i < 8; ++i) { const bool up = lane & 1; const float keep = up ? r[i + 8] : r[i], send = up ? r[i] : r[i + 8]; r[i] = keep + __shfl_xor(send, 1, 64); }
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) { const bool up = lane & 2; const float keep = up ? r[i + 4] : r[i], send = up ? r[i] : r[i + 4]; r[i] = keep + __shfl_xor(send, 2, 64); }
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) { const bool up = lane & 4; const float keep = up ? r[i + 2] : r[i], send = up ? r[i] : r[i + 2]; r[i] = keep + __shfl_xor(send, 4, 64); }
+                        { const bool up = lane & 8; const float keep = up ? r[1] : r[0], send = up ? r[0] : r[1]; r[0] = keep + __shfl_xor(send, 8, 64); }
+                        float x = r[0];
+                        x += __shfl_xor(x, 16, 64);
+                        x += __shfl_xor(x, 32, 64);
+#pragma unroll
+                        for (int off = 1; off < 64; off <<= 1) x16 += __shfl_xor(x16, off, 64);
+                        double* ga = gacc + (wave * kLsGroupsRows + gi) * (kMaxCand + 1);
+                        if (lane < 16) ga[((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3)] += (double)x;
+                        if (lane == 0) ga[kMaxCand] += (double)x16;
                     }
-                }
+                }   // gi
             }
-            if (multi) {
-                // wave reduction of the 16 + 1 partial costs: halve the values per lane at every exchange (15 + 2
-                // shuffles for the 16, 6 for f(p1)); lane l < 16 ends up with the wave total of value brev4(l)
-                const int lane = tid & 63, wave = tid >> 6;
-                float r[kMaxCand];
+        }
+        if (EP == EP_LINESEARCH && multi) {   // fold the four waves' accumulators into the state (f(p1) of a group behind its 16 costs)
+            __syncthreads();
+            for (int o = tid; o < ngroups * (kMaxCand + 1); o += 256) {
+                const int gi = o / (kMaxCand + 1), i = o % (kMaxCand + 1);
+                double x = 0.0;
 #pragma unroll
-                for (int i = 0; i < kMaxCand; ++i) r[i] = acc2[i].x + acc2[i].y;
-                float x16 = acc2[kMaxCand].x + acc2[kMaxCand].y;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { const bool up = lane & 1; const float keep = up ? r[i + 8] : r[i], send = up ? r[i] : r[i + 8]; r[i] = keep + __shfl_xor(send, 1, 64); }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { const bool up = lane & 2; const float keep = up ? r[i + 4] : r[i], send = up ? r[i] : r[i + 4]; r[i] = keep + __shfl_xor(send, 2, 64); }
-#pragma unroll
-                for (int i = 0; i < 2; ++i) { const bool up = lane & 4; const float keep = up ? r[i + 2] : r[i], send = up ? r[i] : r[i + 2]; r[i] = keep + __shfl_xor(send, 4, 64); }
-                { const bool up = lane & 8; const float keep = up ? r[1] : r[0], send = up ? r[0] : r[1]; r[0] = keep + __shfl_xor(send, 8, 64); }
-                float x = r[0];
-                x += __shfl_xor(x, 16, 64);
-                x += __shfl_xor(x, 32, 64);
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) x16 += __shfl_xor(x16, off, 64);
-                double* ga = gacc + (wave * kLsGroupsRows + gi) * (kMaxCand + 1);
-                if (lane < 16) ga[((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3)] += (double)x;
-                if (lane == 0) ga[kMaxCand] += (double)x16;
+                for (int w = 0; w < 4; ++w) x += gacc[(w * kLsGroupsRows + gi) * (kMaxCand + 1) + i];
+                vals[o] = x;
             }
-            }   // gi
         }
-    }
-    if (EP == EP_LINESEARCH && multi) {   // fold the four waves' accumulators into the state (f(p1) of a group behind its 16 costs)
-        __syncthreads();
-        for (int o = tid; o < ngroups * (kMaxCand + 1); o += 256) {
-            const int gi = o / (kMaxCand + 1), i = o % (kMaxCand + 1);
-            double x = 0.0;
+        if (EP == EP_CROSS) return;
+        if (EP == EP_STATS_M && !a.sums) return;
+        if (!(EP == EP_LINESEARCH && multi)) {
+            if (LS) {
 #pragma unroll
-            for (int w = 0; w < 4; ++w) x += gacc[(w * kLsGroupsRows + gi) * (kMaxCand + 1) + i];
-            vals[o] = x;
+                for (int i = 0; i < NACC; ++i) acc[i] = acc2[i].x + acc2[i].y;
+            }
+            // ---- block reduction (float partials -> double) in a fixed order: shuffle tree per wave, waves in index order
+            const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+            for (int i = 0; i < NACC; ++i) {
+                double x = (double)acc[i];
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) x += __shfl_down(x, off, 64);
+                if (lane == 0) red[wave * NACC + i] = x;
+            }
+            __syncthreads();
+            if (tid < NACC) {
+                const double x = red[tid] + red[NACC + tid] + red[2 * NACC + tid] + red[3 * NACC + tid];
+                if (!LS || tid < ncand || tid == kMaxCand)
+                    vals[(LS ? grp * (kMaxCand + 1) : 0) + (LS && tid == kMaxCand ? ncand : tid)] = x;
+            }
+            __syncthreads();
         }
-    }
-    if (EP == EP_CROSS) return;
-    if (EP == EP_STATS_M && !a.sums) return;
-    if (!(EP == EP_LINESEARCH && multi)) {
-    if (LS) {
-#pragma unroll
-        for (int i = 0; i < NACC; ++i) acc[i] = acc2[i].x + acc2[i].y;
-    }
-    // ---- block reduction (float partials -> double) in a fixed order: shuffle tree per wave, waves in index order
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int i = 0; i < NACC; ++i) {
-        double x = (double)acc[i];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) x += __shfl_down(x, off, 64);
-        if (lane == 0) red[wave * NACC + i] = x;
-    }
-    __syncthreads();
-    if (tid < NACC) {
-        const double x = red[tid] + red[NACC + tid] + red[2 * NACC + tid] + red[3 * NACC + tid];
-        if (!LS || tid < ncand || tid == kMaxCand)
-            vals[(LS ? grp * (kMaxCand + 1) : 0) + (LS && tid == kMaxCand ? ncand : tid)] = x;
-    }
-    __syncthreads();
-    }
     }   // grp
     // ---- totals over the workgroups in a fixed order; the last workgroup to arrive publishes them ----------
     int nv = LS ? (ngroups - 1) * (kMaxCand + 1) + ncand + 1 : NACC, nmax = 0;   // line search: costs[.. ncand] of the last group, no further

@@ -219,10 +219,10 @@ __device__ __forceinline__ void wave_lds_fence() {
 }
 // Synchronisation between the steps of ONE row transform in the row kernels: the T threads of a row exchange through
 // their own LDS row only, and for T <= 64 (N <= 1024) they are lanes of one wave -- no workgroup barrier is needed,
-// the waves of a workgroup run their rows independently.
-template <int T>
+// the waves of a workgroup run their rows independently.  WG: the workgroup barrier whatever T is (k_lines_bluestein).
+template <int T, bool WG = false>
 __device__ __forceinline__ void row_sync() {
-    if constexpr (T <= 64 && 64 % T == 0) wave_lds_fence();
+    if constexpr (!WG && T <= 64 && 64 % T == 0) wave_lds_fence();
     else __syncthreads();
 }
 

@@ -23,6 +23,8 @@
 //
 // Reading order: ptycho_common.hpp first (arguments, and what the run-structured column kernels share: run bounds and
 // decode, tile address, accumulate; run_split.hpp is the host's half of the run structure), then the kernel headers (k_*.hpp;
+// k_rows.hpp opens with row_steps, the forward row transform that its fused CG stages, k_rows_split and the Bluestein lines of
+// k_generic.hpp share, and holds TrialTerm, the line-search term of both likelihoods;
 // frame_part.hpp before the analysis ones, which share its (frame, pixel) partition, fold and block sum), then
 // the host side by topic -- host_handle.hpp (handle, errors, profiler,
 // allocations, dispatch macros, the host's half of the partition), host_ops.hpp (launchers and the three operators), host_cg.hpp (CG stages) -- and
