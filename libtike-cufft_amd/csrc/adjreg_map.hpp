@@ -123,4 +123,42 @@ PTY_FN void adjreg_combine(c32* acc, const c32* tile, const AdjRegWin& w, int g,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Tile ring of k_cols_adjreg<256, split>: the strip tile of the NEXT position (N rows x C columns, 32 KiB) is requested by
+// LDS-DMA (global_load_lds_dwordx4: 16 bytes per lane, no register destination) into one LDS segment per wave.  A wave
+// requests exactly the rows its own threads consume, so its own wait orders the ring and no barrier is involved.
+//   thread tid = (c = tid % C, j0 = tid / C) consumes rows j0 + m T, m < E (Fft::load of a radix-16 step);
+//   a wave holds four consecutive j0: 64 rows x 128 B = PIECES requests of 1 KiB;
+//   lane L of request i supplies row rr = 8 i + L / 8 of the wave's rows (rr = 4 m + j0 % 4), column pair L % 8;
+//   the hardware writes the request lane-linearly (segment + 1 KiB i + 16 L bytes): the image is [64 rows][16 columns],
+//   and thread tid finds its element m at word 64 m + tid % 64 of the segment (consecutive lanes, consecutive words).
+// ---------------------------------------------------------------------------
+template <int N_>
+struct AdjRingCfg {
+    static constexpr int N = N_, C = 16, E = 16, T = N / E;
+    static constexpr int WAVE = 64, NW = T * C / WAVE;   // waves per workgroup
+    static constexpr int JW = WAVE / C;                  // j0 values per wave
+    static constexpr int PIECES = 8;                     // requests per wave and tile
+    static constexpr int PIECE = WAVE * 2;               // elements per request (16 bytes per lane)
+    static constexpr int SEG = PIECES * PIECE;           // elements per wave segment
+    static constexpr int RING = NW * SEG;                // elements in all
+    static constexpr int ROW_STEP = (WAVE / 8 / JW) * T; // source rows between a lane's requests i and i + 1
+    static_assert(RING == N * C && SEG == JW * E * C, "the ring holds one strip tile");
+};
+
+// source of lane `lane` in request i of wave `wave`: tile row, and first of its two strip columns
+template <class R>
+PTY_FN int adjring_src_row(int wave, int i, int lane) {
+    const int rr = 8 * i + lane / 8;
+    return wave * R::JW + rr % R::JW + (rr / R::JW) * R::T;
+}
+template <class R>
+PTY_FN int adjring_src_col(int lane) { return 2 * (lane % 8); }
+// ring element the hardware writes that lane's first column to (the second follows it)
+template <class R>
+PTY_FN int adjring_dst_slot(int wave, int i, int lane) { return wave * R::SEG + i * R::PIECE + 2 * lane; }
+// ring element that holds thread tid's point m (tile row tid / C + m T, strip column tid % C)
+template <class R>
+PTY_FN int adjring_read_slot(int tid, int m) { return (tid / R::WAVE) * R::SEG + m * R::WAVE + tid % R::WAVE; }
+
 }  // namespace pty

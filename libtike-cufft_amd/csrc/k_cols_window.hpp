@@ -28,8 +28,9 @@ struct WinCfg {
 // positions (0.79 / 1.37 / 2.61 against 0.77 / 1.23 / 2.32 ms per iteration, profiles/r04/narrow_strips.txt); not instantiated.
 template <int N, bool SPLIT = false, int CW = 0>
 __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_adjwin(const ColArgs a, const int seglen) {
-    // SPLIT (N = 256): the tile already went through the first radix-16 step in k_rows_split;
-    // only the twiddled second step runs here, straight from global memory (no exchange).
+    // SPLIT (N = 256): the tile already went through the first radix-16 step and the inter-step twiddle in
+    // k_rows_split; only the second radix-16 step runs here, straight from global memory (no exchange).
+    static_assert(!SPLIT || N == 256, "split column pass is written for the 16 x 16 plan");
     using P = Plan<N>;
     using F = Fft<P, +1>;
     constexpr int E = P::E, T = P::T, C = CW ? CW : ColCfg<N>::C, NT = T * C;
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
         STAMP_DRAIN();
         STAMP(1)          // wait for the tile loads
         if (SPLIT) {
-            fft.template compute<LAST>(v);   // twiddle + radix 16: the step k_rows_split left
+            fft.template compute<0>(v);   // radix 16, constant twiddles only: the step k_rows_split left
         } else {
         fft.template compute<0>(v);
         if (P::NSTEP > 1) {
@@ -280,11 +281,21 @@ __global__ __launch_bounds__(Plan<N>::T * ColCfg<N>::C, 2) void k_cols_adjreg(co
     using W = AdjRegCfg<N, NT>;
     static_assert(C == W::C, "strip width");
     constexpr int WC = W::WC, G = W::G, RPG = W::RPG;
-    // exchange buffer = T tile (W::TILE: zero border, see adjreg_map.hpp); only the tile's own elements are ever written
-    __shared__ c32 lds[W::TILE];
+    // SPLIT (N = 256): k_rows_split left one radix-16 step with constant twiddles, and the strip tile of the next position
+    // streams through a ring in LDS filled by LDS-DMA (AdjRingCfg, adjreg_map.hpp) instead of waiting in 32 registers:
+    // its requests are outstanding from the moment the current tile has been read out of the ring until the top of
+    // the next position, across both barriers, where register loads could only be issued after the T store.
+    static_assert(!SPLIT || N == 256, "split column pass is written for the 16 x 16 plan");
+    using R = AdjRingCfg<N>;
+    constexpr int RINGN = SPLIT ? R::RING : 0;
+    // the ring FIRST: its LDS-DMA destination goes through M0, and the low addresses are in reach of every form of it.
+    // Behind it the exchange buffer = T tile (W::TILE: zero border, see adjreg_map.hpp); only the tile's own elements
+    // are ever written
+    __shared__ __attribute__((aligned(SPLIT ? 16 : 8))) c32 ring_tile[RINGN + W::TILE];
+    c32* const lds = ring_tile + RINGN;
     // the accumulators take the registers the inter-step twiddles had in k_cols_adjwin: a set is re-read from this copy of
-    // the table right before the step that uses it (same values, k_cols_argmax does the same)
-    __shared__ c32 wtab[N];
+    // the table right before the step that uses it (same values, k_cols_argmax does the same); un-split only
+    __shared__ c32 wtab[SPLIT ? 1 : N];
     __shared__ c32 stage[W::STAGE];   // the rows on their way out of a window that slides by one group
 
     const int tid = threadIdx.x;
@@ -302,8 +313,42 @@ __global__ __launch_bounds__(Plan<N>::T * ColCfg<N>::C, 2) void k_cols_adjreg(co
     auto at = [&](int i) { return (i + 1) * W::P + c + W::COL0; };
 
     F fft;
-    for (int o = tid; o < N; o += NT) wtab[o] = a.table[o];
+    if constexpr (!SPLIT) {
+        for (int o = tid; o < N; o += NT) wtab[o] = a.table[o];
+    }
     for (int o = tid; o < W::TILE; o += NT) lds[o] = zero;
+
+    // ---- tile ring (SPLIT): this wave's segment, its lanes' source offset, request and read-out ----------------------
+    // The requests are inline assembly, so the compiler neither counts them nor waits for them: the waits are the
+    // explicit ones below.  (Its own vmcnt waits stay safe: more operations outstanding only make them wait longer.)
+    const int lane = tid % R::WAVE, wave = uni_i(tid / R::WAVE);
+    const unsigned ring_m0 = (unsigned)(size_t)ring_tile + (unsigned)(wave * R::SEG * (int)sizeof(c32));   // LDS byte address
+    const unsigned ring_voff =
+        (unsigned)((adjring_src_row<R>(wave, 0, lane) * N + x0 + adjring_src_col<R>(lane)) * (int)sizeof(c32));
+    const int ring_rd = adjring_read_slot<R>(tid, 0);
+    auto ring_request = [&](const c32* tile_in) {   // R::PIECES x 1 KiB: rows ROW_STEP apart per lane, LDS lane-linear
+#pragma unroll
+        for (int i = 0; i < R::PIECES; ++i) {
+            const c32* sb = tile_in + (size_t)i * R::ROW_STEP * N;
+            const unsigned dst = ring_m0 + (unsigned)(i * R::PIECE * (int)sizeof(c32));
+            unsigned keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(ring_voff), "s"(sb), "s"(dst) : "memory");
+        }
+    };
+    // (after the wave's own vmcnt(0): nothing else orders a ds_read behind a pending LDS-DMA) read the tile out and wait
+    // for the reads: the segment is then free for the next request
+    auto ring_read = [&](c32* v) {
+#pragma unroll
+        for (int m = 0; m < E; ++m) v[m] = ring_tile[ring_rd + m * R::WAVE];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
+    // workgroup barrier that leaves the ring's requests in flight (__syncthreads() would wait for them): LDS only
+    auto ring_barrier = [&]() {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
 
     c32 pr[E];   // c * probe strip, natural order (row j0 + m*T); zero on padding
     int cur_t = -1;
@@ -351,27 +396,36 @@ __global__ __launch_bounds__(Plan<N>::T * ColCfg<N>::C, 2) void k_cols_adjreg(co
     STAMP_DECL
     RunSt st = decode(kb);
     c32 v[E];
+    // The tile of position k reaches v[] as the rows of Fft::load: un-split by register loads, issued a position ahead
+    // after the T store (written out at the three sites: through a lambda these instantiations take ten more registers);
+    // SPLIT through the ring -- the first tile of a run is requested here, before the probe strip is loaded
     if (st.have && st.q.valid) {
         const c32* tile_in = tile_of(st, kb);
-        if (a.nt & 8)
-            fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return __builtin_nontemporal_load(tile_in + (size_t)i * N + x); });
-        else
-            fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
+        if constexpr (SPLIT) {
+            ring_request(tile_in);
+        } else {
+            if (a.nt & 8)
+                fft.template load<0>(v, j0, [&](int i) { return __builtin_nontemporal_load(tile_in + (size_t)i * N + x); });
+            else
+                fft.template load<0>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
+        }
     }
     for (int k = kb; k < ke; ++k) {
         RunSt nx = decode(k + 1);
-        if (!st.q.valid) {   // skipped position: nothing to add; fetch the next tile
+        if (!st.q.valid) {   // skipped position: nothing to add (SPLIT: nothing in flight, nothing to wait for); fetch the next tile
             if (nx.have && nx.q.valid) {
                 const c32* tile_in = tile_of(nx, k + 1);
-                fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
+                if constexpr (SPLIT) ring_request(tile_in);
+                else fft.template load<0>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
             }
             st = nx;
             continue;
         }
         const Pos q = st.q;
         int jz = j0;
-        asm volatile("" : "+v"(jz));   // opaque copy: keeps the twiddle reads inside the position loop
+        asm volatile("" : "+v"(jz));   // opaque copy: keeps the twiddle reads inside the position loop (un-split)
         if (st.t != cur_t) {
+            // (SPLIT: ordinary loads beside the ring -- the compiler's wait for them also waits for the tile: once per angle)
             const c32* prb = a.aux + (size_t)st.t * ge.nprb * ge.nprb;
 #pragma unroll
             for (int m = 0; m < E; ++m) {
@@ -382,14 +436,20 @@ __global__ __launch_bounds__(Plan<N>::T * ColCfg<N>::C, 2) void k_cols_adjreg(co
             }
             cur_t = st.t;
         }
-        // ---- inverse DFT over y of this strip (tile already in v) ----------------------
+        // ---- inverse DFT over y of this strip ---------------------------------------------
         STAMP(0)          // loop head, decode, probe strip
-        STAMP_DRAIN();
-        STAMP(1)          // wait for the tile loads
-        if (SPLIT) {
-            fft.template init_step<LAST>(jz, wtab);
-            fft.template compute<LAST>(v);   // twiddle + radix 16: the step k_rows_split left
+        if constexpr (SPLIT) {
+            // own requests landed (vmcnt counts this wave's atomics of the last position too) -> tile out of the ring -> the
+            // segment is free: the next tile is requested at once and stays in flight across both barriers of the position
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            STAMP(1)      // wait for the tile
+            ring_read(v);
+            if (nx.have && nx.q.valid) ring_request(tile_of(nx, k + 1));
+            STAMP(9)      // ring read-out + request issue
+            fft.template compute<0>(v);   // radix 16, constant twiddles only: the step k_rows_split left
         } else {
+            STAMP_DRAIN();
+            STAMP(1)      // wait for the tile loads
             fft.template compute<0>(v);
             if (P::NSTEP > 1) {
                 fft.template store<0>(v, j0, [&](int i, c32 val) { lds[at(i)] = val; });
@@ -419,21 +479,23 @@ __global__ __launch_bounds__(Plan<N>::T * ColCfg<N>::C, 2) void k_cols_adjreg(co
             // split kernel: no exchange went through the tile, so the "previous combine is done"
             // barrier sits here, after this position's transform, instead of at the end of the loop
             STAMP(2)      // transform + probe product
-            if (SPLIT) __syncthreads();
+            if constexpr (SPLIT) ring_barrier();
             STAMP(3)      // barrier: previous combine done
 #pragma unroll
             for (int m = 0; m < E; ++m) lds[at(j0 + m * T)] = nat[m];
         }
         STAMP(8)          // T store
-        // prefetch the next tile while the combine runs
-        if (nx.have && nx.q.valid) {
-            const c32* tile_in = tile_of(nx, k + 1);
-            if (a.nt & 8)
-                fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return __builtin_nontemporal_load(tile_in + (size_t)i * N + x); });
-            else
-                fft.template load<(SPLIT ? 1 : 0)>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
+        if constexpr (!SPLIT) {
+            // prefetch the next tile while the combine runs
+            if (nx.have && nx.q.valid) {
+                const c32* tile_in = tile_of(nx, k + 1);
+                if (a.nt & 8)
+                    fft.template load<0>(v, j0, [&](int i) { return __builtin_nontemporal_load(tile_in + (size_t)i * N + x); });
+                else
+                    fft.template load<0>(v, j0, [&](int i) { return tile_in[(size_t)i * N + x]; });
+            }
+            STAMP(9)      // prefetch issue
         }
-        STAMP(9)          // prefetch issue
         // ---- window bookkeeping (workgroup-uniform) and retire: registers only, no barrier ----
         const int Xa = q.sx + x0 - ge.pad;   // object column of strip column cc = 0
         const int nret = adjreg_retire_count<W>(w, st.t, Xa, q.sy);
@@ -449,7 +511,9 @@ __global__ __launch_bounds__(Plan<N>::T * ColCfg<N>::C, 2) void k_cols_adjreg(co
             adjreg_advance<W>(w, nret, st.t, q.sx, q.sy, x0 - ge.pad);
         }
         STAMP(4)          // window bookkeeping, retire
-        __syncthreads();   // T tile complete, staged rows visible
+        // T tile complete, staged rows visible
+        if constexpr (SPLIT) ring_barrier();
+        else __syncthreads();
         STAMP(5)          // barrier: T tile complete
         for (int o = tid; o < nstaged * RPG * WC; o += NT) add_to_object(stage[o], was.t, was.Ybase + o / WC, was.X0 + o % WC);
         if (g < G) adjreg_combine<W>(acc, lds, w, g, cw, Xa, q.sy, ge.pad, q.fy, q.fx);
@@ -517,8 +581,8 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
     // out of the position loop measured SLOWER -- 1.24 -> 1.49 ms per pass at 4096 x 256^2 -- so every NM > 1 takes this path.)
     __shared__ c32 wtab[NM > 1 ? N : 1];
     F fft;
-    if (NM == 1) fft.init(j0, a.table);
-    else for (int o = tid; o < N; o += NT) wtab[o] = a.table[o];
+    if (NM > 1) for (int o = tid; o < N; o += NT) wtab[o] = a.table[o];
+    else if (!SPLIT) fft.init(j0, a.table);   // split: the inter-step twiddle is k_rows_split's, either direction
     for (int o = tid; o < (H + 1) * WC; o += NT) win[o] = zero;
 
     // FWD: c * probe strip in step-0 slot order (zero on padding -> masks the gather);
@@ -671,7 +735,7 @@ __global__ __launch_bounds__(Plan<N>::T * (CW ? CW : ColCfg<N>::C)) void k_cols_
             }
             const St cur = prepare_issue(k, ke);   // same decode as st, plus the window update
             if (SPLIT) {
-                fft.template compute<LAST>(v);
+                fft.template compute<0>(v);   // radix 16, constant twiddles only (k_rows_split applied the inter-step twiddle)
             } else if (P::NSTEP > 1) {
                 fft.template load<1>(v, j0, [&](int i) { return lds[i * C + c]; });
                 if (P::NSTEP > 2) {

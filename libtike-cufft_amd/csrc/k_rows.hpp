@@ -101,7 +101,10 @@ __global__ __launch_bounds__(256) void k_rows(const RowArgs a) {
 //   DIR < 0 (forward): rows j' + 16 t of the intermediate -> twiddle -> radix 16 over t
 //                      -> transpose through LDS -> DFT over x -> final rows j' + 16 t'.
 //   DIR > 0 (adjoint): rows j' + 16 f of g -> IDFT over x -> transpose -> radix 16 over
-//                      the 16 rows (step 0, no twiddle) -> intermediate rows 16 j' + k1.
+//                      the 16 rows (step 0, no twiddle) -> step 1's twiddle W^{-j' k1} -> intermediate
+//                      rows 16 j' + k1.
+// Either way the inter-step twiddle is applied here, so the split column kernels run a radix-16 step with constant
+// twiddles only.
 // ---------------------------------------------------------------------------
 template <int N, int DIR>
 __global__ __launch_bounds__(256) void k_rows_split(const RowArgs a) {
@@ -152,6 +155,9 @@ __global__ __launch_bounds__(256) void k_rows_split(const RowArgs a) {
         } else {
             // ---- IDFT over x of row jp + 16 f of g ------------------------------------------
             const c32* srow = sbase + (size_t)(jp + 16 * f) * N;
+            // the item's 16 inter-step twiddles (below), one per lane (k1 = lane % 16), requested ahead of the row: the
+            // table is read by vector loads in this loop, and 16 of them at the point of use wait for one another
+            const c32 wl = cconj(a.table[(jp * (tid & 15)) & (N - 1)]);   // conjugated as Fft::init keeps them
             fft.template load<0>(v, j0, [&](int i) { return __builtin_nontemporal_load(srow + i); });
             fft.template compute<0>(v);
             fft.template store<0>(v, j0, put);
@@ -166,6 +172,18 @@ __global__ __launch_bounds__(256) void k_rows_split(const RowArgs a) {
 #pragma unroll
             for (int t = 0; t < 16; ++t) v[t] = lds[L::at(t, x)];
             fft_reg<16, +1>(v);
+            // inter-step twiddle of the IDFT over y, as the forward branch has it before its step: intermediate row
+            // 16 jp + k1 is input t = jp of the column thread j0 = k1, which would multiply it by conj(table[j0 t])
+            // for t >= 1 (Fft::compute).  The same cmul on the same values here, the factor a scalar operand (lane k1 of
+            // wl), leaves the column kernels a radix-16 step with constant twiddles only.
+            if (jp != 0) {
+#pragma unroll
+                for (int k1 = 0; k1 < 16; ++k1) {
+                    const c32 w = c32{__int_as_float(__builtin_amdgcn_readlane(__float_as_int(wl.x), k1)),
+                                      __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wl.y), k1))};
+                    v[brev(k1, 4)] = cmul(v[brev(k1, 4)], w);
+                }
+            }
             if (x >= a.wa && x < a.wb) {
 #pragma unroll
                 for (int k1 = 0; k1 < 16; ++k1)

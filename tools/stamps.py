@@ -30,13 +30,13 @@ torch.cuda.synchronize()
 prof = slv.profile_read()
 assert dbg(slv._h, buf) == 0
 names = {0: ["loop head", "gather (LDS taps + weights)", "probe product + radix-16", "store issue", "barrier A", "window update", "barrier B", "-", "-", "-", "-", "-"],
-         1: ["loop head / probe strip", "wait for tile loads", "radix-16 + probe product", "barrier (prev. combine done)", "window bookkeeping + retire", "barrier (T complete)", "staged rows to the object + combine", "final retire", "T store", "prefetch issue", "-", "-"]}
+         1: ["loop head / probe strip", "wait for tile loads", "radix-16 + probe product", "barrier (prev. combine done)", "window bookkeeping + retire", "barrier (T complete)", "staged rows to the object + combine", "final retire", "T store", "prefetch issue (split: ring read-out + request issue)", "-", "-"]}
 for role, title in ((0, "k_cols_gatherwin<%d,FWD%s>" % (ND, ",split" if ND == 256 else "")), (1, "k_cols_adjreg<%d%s>" % (ND, ",split" if ND == 256 else ""))):
     v = np.array([buf[12 * role + i] for i in range(12)], dtype=np.float64)
     tot = v.sum()
     print(title, " total wave-cycles per launch %.3e" % (tot / reps))
     for i in range(12):
         if v[i]:
-            print("   %-36s %5.1f %%   %8.0f cycles per wave and position" % (names[role][i], 100 * v[i] / tot, v[i] / reps / (4096 * (ND // 16) * (4 if ND == 256 else 8))))
+            print("   %-58s %5.1f %%   %8.0f cycles per wave and position" % (names[role][i], 100 * v[i] / tot, v[i] / reps / (4096 * (ND // 16) * (4 if ND == 256 else 8))))
 for k, (ms, cnt) in prof.items():
     print("%-24s %.3f ms per launch" % (k, ms / cnt))
