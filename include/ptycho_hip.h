@@ -271,6 +271,44 @@ int ptycho_unwrap_finish(float* out, double* state, const float* buf, const floa
 int ptycho_unwrap_residues(signed char* charge, long long* count, const float* phase, const float* weight, size_t ptheta,
                            size_t nz, size_t n, void* stream);
 
+/* Free-space propagation of square complex fields and the figures of a focus series (libtike.hipfft.propagate).  h is
+ * a handle whose ndet is the side S of the fields, as for ptycho_fft2; it supplies the twiddle table and nothing of it is
+ * changed.  Any side ptycho_fft2 takes from 16 up: 16 <= S <= 1024, or 2048.  Everything runs on `stream`, nothing
+ * synchronises, no float atomics and fixed summation orders: the same inputs on the same path give the same bits.
+ * A field u is complex64 [S][S] in image layout; nothing is shifted: spec is its UNNORMALISED forward DFT
+ * (ptycho_fft2, dir = -1) with DC at [0][0], and H is indexed the same way.  With k = fftfreq(S) S the integer
+ * frequencies, k2 = ky^2 + kx^2, q = q0 k2 (q0 = (lambda / (S p))^2, p the pixel size of the field's plane) and
+ * zl = z / lambda, all float64, the transfer function in turns is
+ *   method 0, Fresnel (paraxial):                     t = -zl q / 2,                |H| = 1;
+ *   method 1, angular spectrum, carrier removed:      t = -zl q / (1 + sqrt(1 - q)) for q <= 1 (the cancellation-free
+ *                                                     form of zl (sqrt(1 - q) - 1)), |H| = 1; H = 0 for q > 1
+ *                                                     (evanescent), whatever the sign of z.
+ * t -= rint(t) in float64 (zl q reaches 1e7 turns and more), H = exp(2 pi i t) by sincospi(2 t) in float64, times 1 / S^2,
+ * rounded once to float32; every product and sum that forms t is rounded on its own (no fused multiply-add).
+ *   plane[f][d] = IDFT(spec[f] H_d)       (complex64; z = 0 gives u back; the convolution is circular: padding is the
+ *                                          caller's)
+ *   metrics[f][d][8] (float64), with v = |plane|^2 formed in float32 as round(round(re re) + round(im im)), converted to
+ *   double, and y, x the pixel indices 0 ... S - 1:
+ *       { sum v, sum v^2, sum v y, sum v x, sum v y^2, sum v x^2, max v, flat index y S + x of the first maximum }.
+ *   A NaN v is skipped by the max, as in ptycho_prepare_frames, and propagates into the sums; if no v compares, the max
+ *   is -inf and the index -1.  Of equal maxima the one with the lowest index counts.
+ * Arguments: spec complex64 [nfield][S][S]; zl float64 [nplane] ON THE DEVICE; planes complex64 [nfield][nplane][S][S]
+ * or NULL; metrics float64 [nfield][nplane][8] or NULL (not both NULL); work float64 scratch of
+ * ptycho_propagate_work_words(h, nfield, nplane, planes != NULL) words -- the count may be 0: pass any non-null pointer
+ * then; it is 0 for sizes out of range.
+ * Two paths, chosen as ptycho_fft2 chooses.  Sides with a plan whose tile fits a compute unit's LDS (16, 32, 48, 64, 80,
+ * 96, 112, 128) with option "tile" on: ONE launch, the spectrum times H_d, both inverse passes and the figures of a pair
+ * (f, d) stay on the compute unit, and a plane is written only if planes is given; no scratch.  Every other side, and those
+ * sides with "tile" off: spec H_d into planes (or into work when planes is NULL), the in-place inverse transform of
+ * ptycho_fft2, and one workgroup per pair for the figures.  The two paths add in different orders: their sums agree to
+ * rounding, their maxima and indices exactly when their planes do.
+ * PTYCHO_ERR_ARG, before any HIP call, for a null or freed handle, a null spec / zl / work, planes and metrics both
+ * null, S < 16 (or S = 1025 ... 2047), nfield or nplane zero, nfield * nplane >= 2^30, a method other than 0 and 1, a q0
+ * that is negative or not finite, spec or planes not 16-byte aligned. */
+size_t ptycho_propagate_work_words(ptycho_handle h, size_t nfield, size_t nplane, int planes_wanted);
+int ptycho_propagate(ptycho_handle h, void* planes, double* metrics, const void* spec, size_t nfield, const double* zl,
+                     size_t nplane, double q0, int method, void* work, void* stream);
+
 /* ---- fused CG-stage entry points ("plus fused CG-stage entry points") ----
  * The elementwise stages of CGPtychoSolver.run (src/libtike/cufft/ptycho.py:325-393) are
  * fused into the row pass of the DFT so that farplanes are never materialised.  The

@@ -64,6 +64,7 @@ namespace {
 #include "k_generic.hpp"
 #include "k_zoom.hpp"
 #include "k_tile.hpp"
+#include "k_propagate.hpp"
 }  // namespace
 
 #include "host_handle.hpp"
@@ -73,6 +74,7 @@ namespace {
 #include "host_fit.hpp"
 #include "host_prepare.hpp"
 #include "host_unwrap.hpp"
+#include "host_propagate.hpp"
 
 extern "C" {
 
@@ -864,6 +866,31 @@ int ptycho_unwrap_residues(signed char* charge, long long* count, const float* p
     if (!count || !phase) return fail(PTYCHO_ERR_ARG, "count and phase must not be null");
     if (int rc = unwrap_check_sizes(ptheta, nz, n)) return rc;
     return do_unwrap_residues(charge, count, phase, weight, (int)ptheta, (int)nz, (int)n, (hipStream_t)stream);
+}
+
+// ---- free-space propagation and focus-series figures (k_propagate.hpp, libtike.hipfft.propagate) -------------------------
+size_t ptycho_propagate_work_words(ptycho_handle h, size_t nfield, size_t nplane, int planes_wanted) {
+    if (!h || h->freed || !prop_sizes_ok((size_t)h->ge.ndet, nfield, nplane)) return 0;
+    if (planes_wanted || prop_fused(h)) return 0;
+    return nfield * nplane * (size_t)h->ge.ndet * (size_t)h->ge.ndet;   // one complex64 per float64 word
+}
+
+int ptycho_propagate(ptycho_handle h, void* planes, double* metrics, const void* spec, size_t nfield, const double* zl,
+                     size_t nplane, double q0, int method, void* work, void* stream) {
+    int rc = check_args(h);
+    if (rc) return rc;
+    if (!spec || !zl || !work) return fail(PTYCHO_ERR_ARG, "spec, zl and work must not be null");
+    if (!planes && !metrics) return fail(PTYCHO_ERR_ARG, "nothing to compute: planes and metrics are both null");
+    if (!frc_size_ok(h->ge.ndet)) return fail(PTYCHO_ERR_ARG, "the handle's ndet must be in [16, 1024] or 2048");
+    if (nfield == 0 || nplane == 0) return fail(PTYCHO_ERR_ARG, "nfield and nplane must be positive");
+    if (!prop_sizes_ok((size_t)h->ge.ndet, nfield, nplane)) return fail(PTYCHO_ERR_ARG, "nfield * nplane must stay below 2^30");
+    if (method != 0 && method != 1) return fail(PTYCHO_ERR_ARG, "method must be 0 (fresnel) or 1 (angular spectrum)");
+    if (!(q0 >= 0.0) || !(q0 < INFINITY)) return fail(PTYCHO_ERR_ARG, "q0 must be finite and not negative");
+    if (!aligned16(spec) || !aligned16(planes)) return fail(PTYCHO_ERR_ARG, "spec and planes must be 16-byte aligned");
+    const PropArgs a{(c32*)planes, metrics, (const c32*)spec, zl, (c32*)work, (long long)nfield, (long long)nplane, q0, method};
+    hipStream_t st = (hipStream_t)stream;
+    if (h->bs_m) { PTY_DISPATCH_POW2(h->bs_m, (do_propagate_generic<NN>(h, a, st))); }
+    PTY_DISPATCH(h->ge.ndet, (do_propagate<NN>(h, a, st)));
 }
 
 }  // extern "C"

@@ -6,5 +6,6 @@ from libtike.hipfft.gauge import illumination, fit_gauge, apply_gauge, fix_gauge
 from libtike.hipfft.fit import fit_frames, accumulate_intensity, flag_frames  # noqa: F401
 from libtike.hipfft.prepare import prepare_frames, initial_probe  # noqa: F401
 from libtike.hipfft.unwrap import unwrap_phase, phase_residues  # noqa: F401
+from libtike.hipfft.propagate import propagate, focus_series, object_pixel_size  # noqa: F401
 
 __version__ = "0.1.0"

@@ -33,6 +33,7 @@ SYMBOLS = ("ptycho_create", "ptycho_free", "ptycho_destroy", "ptycho_get",
            "ptycho_prepare_work_words", "ptycho_prepare_frames",
            "ptycho_unwrap_work_words", "ptycho_unwrap_buffer_floats", "ptycho_unwrap_begin", "ptycho_unwrap_iterate",
            "ptycho_unwrap_finish", "ptycho_unwrap_residues",
+           "ptycho_propagate_work_words", "ptycho_propagate",
            "ptycho_last_error", "ptycho_version")
 
 if not os.path.exists(LIB_PATH):
@@ -132,6 +133,13 @@ unwrap_iterate = _sig("ptycho_unwrap_iterate", _i, _vp, _vp, _vp, _sz, _sz, _sz,
 unwrap_finish = _sig("ptycho_unwrap_finish", _i, _vp, _vp, _vp, _vp, _vp, _i, _sz, _sz, _sz, _vp, _vp)
 #: charge, count, phase, weight, ptheta, nz, n, stream
 unwrap_residues = _sig("ptycho_unwrap_residues", _i, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp)
+#: propagation (handle of ndet = S): h, nfield, nplane, planes_wanted -> float64 words of ``propagate``'s scratch
+propagate_work_words = _sig("ptycho_propagate_work_words", _sz, _vp, _sz, _sz, _i)
+#: h, planes, metrics, spec, nfield, zl, nplane, q0, method, work, stream
+propagate = _sig("ptycho_propagate", _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, ctypes.c_double, _i, _vp, _vp)
+#: ``method`` codes of ``propagate`` and the float64 words it leaves per (field, plane)
+PROPAGATE_METHODS = {"fresnel": 0, "angular": 1}
+PROPAGATE_WORDS = 8
 #: float64 words of the unwrapper's state per angle (PTYCHO_UNWRAP_STATE_WORDS) and the slots the wrapper reads
 UNWRAP_STATE_WORDS = 16
 UNWRAP_ITER, UNWRAP_STATUS, UNWRAP_RELRES, UNWRAP_C = 5, 6, 7, 8
