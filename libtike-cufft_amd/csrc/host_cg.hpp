@@ -7,43 +7,36 @@ namespace {
 inline int slot_a(ptycho_handle h, int k) { return h->compact_modes ? k : 2 * k; }
 inline int slot_b(ptycho_handle h, int k) { return h->compact_modes ? h->compact_modes : 2 * k + 1; }
 inline bool slot_ready(ptycho_handle h, int slot) { return slot >= 0 && slot < ptycho_handle_s::kSlots && h->work[slot]; }
+template <class... S>
+int need_slots(ptycho_handle h, S... slots) {   // a stage that reads them: an earlier stage filled every one
+    return (... && slot_ready(h, slots)) ? (int)PTYCHO_OK : fail(PTYCHO_ERR_ARG, "work slot is empty");
+}
 int ensure_work(ptycho_handle h, int slot) {   // called by every stage that is about to write the slot
     if (slot < 0 || slot >= ptycho_handle_s::kSlots) return fail(PTYCHO_ERR_ARG, "work slot out of range");
     h->slot_max_ok[slot] = false;
     if (!h->work[slot]) {
         // kMaxModes spare tiles: the M chunk parts of the shared slot of the compact layout take M ceil(total / M) tiles
-        const size_t total = (size_t)h->ge.ptheta * h->ge.nscan + kMaxModes;
+        const size_t total = (size_t)h->ge.npos() + kMaxModes;
         HIP_TRY(hipMalloc((void**)&h->work[slot], total * h->ge.ndet * h->ge.ndet * sizeof(c32)));
         HIP_TRY(hipMemset(h->work[slot], 0, total * h->ge.ndet * h->ge.ndet * sizeof(c32)));
     }
     return PTYCHO_OK;
 }
 
+// allow_split of the stages' column passes (col_path.hpp): never, the fused row stages transform the whole of x
+constexpr bool kCgSplit = false;
+
 // npos_limit > 0: only the first npos_limit positions (natural order = sorted order for whole angles: the sort key is
 // angle major) -- the position correction needs angle 0 only (ptycho.py:399-403)
 template <int N>
 int do_cg_fwd_cols(ptycho_handle h, int slot, const c32* f, const float* scan, const c32* prb, hipStream_t st, long long npos_limit = 0) {
-    const Geom& ge = h->ge;
-    const long long total = (long long)ge.ptheta * ge.nscan;
-    int strip0, nstrips;
-    strip_range<N>(h->ge, strip0, nstrips);
-    const bool window = h->use_window && WinCfg<N>::fits;
-    int rc = PTYCHO_OK;
-    if (window) {
-        rc = sort_positions(h, scan, st);
-        if (rc) return rc;
-    }
-    ColArgs ca{};
-    ca.src = f; ca.dst = h->work[slot]; ca.aux = prb; ca.scan = scan; ca.table = h->table; ca.ge = ge;
-    ca.k_begin = 0; ca.k_end = (int)((npos_limit > 0 && npos_limit < total) ? npos_limit : total); ca.strip0 = strip0; ca.nstrips = nstrips;
-    if (window) {
-        ca.order = h->order;
-        if constexpr (WinCfg<N>::fits) rc = launch_gatherwin<N, M_FWD>(h, ca, st);
-    } else {
-        ca.order = nullptr;
-        rc = launch_cols<N, -1, M_FWD>(h, ca, st);
-    }
-    return rc;
+    const long long total = h->ge.npos();
+    const ColPath path = col_path_for<N>(h, COL_FWD, kCgSplit);
+    int rc = col_path_sorts(path, COL_FWD) ? sort_positions(h, scan, st) : (int)PTYCHO_OK;
+    if (rc) return rc;
+    ColArgs ca = col_args<N>(h, scan, 0, (npos_limit > 0 && npos_limit < total) ? npos_limit : total, path, COL_FWD);
+    ca.src = f; ca.dst = h->work[slot]; ca.aux = prb;
+    return launch_fwd_cols<N>(h, ca, st, kCgSplit);
 }
 
 // finish: 1 = add the result to f / prb (public entry point: the caller zero-filled it); 0 = store it (no zero fill
@@ -51,41 +44,22 @@ int do_cg_fwd_cols(ptycho_handle h, int slot, const c32* f, const float* scan, c
 template <int N>
 int do_cg_adj_cols(ptycho_handle h, int slot, c32* f, const float* scan, c32* prb, int flg, hipStream_t st,
                    const double* known_omax = nullptr, int finish = 1) {
-    const Geom& ge = h->ge;
-    const long long total = (long long)ge.ptheta * ge.nscan;
-    int strip0, nstrips;
-    strip_range<N>(h->ge, strip0, nstrips);
+    const long long total = h->ge.npos();
+    const ColMode mode = flg == 0 ? COL_ADJ_OBJ : COL_ADJ_PRB;
+    const ColPath path = col_path_for<N>(h, mode, kCgSplit);
     int rc = sort_positions(h, scan, st);
     if (rc) return rc;
-    ColArgs ca{};
-    ca.src = h->work[slot]; ca.scan = scan; ca.table = h->table; ca.ge = ge; ca.natural_tiles = 1;
-    ca.order = h->order; ca.k_begin = 0; ca.k_end = (int)total; ca.strip0 = strip0; ca.nstrips = nstrips;
-    const bool window = h->use_window && WinCfg<N>::fits;
+    ColArgs ca = col_args<N>(h, scan, 0, total, path, mode);
+    ca.src = h->work[slot]; ca.natural_tiles = 1; ca.dst = flg == 0 ? f : prb; ca.aux = flg == 0 ? prb : f;
     if (h->deterministic) {
-        if (!window) return fail(PTYCHO_ERR_ARG, "option deterministic needs the windowed adjoint kernels (ndet <= 512)");
-        rc = det_begin(h, ca, h->work[slot], total * N * N, flg == 0 ? prb : f,
-                       flg == 0 ? (long long)ge.ptheta * ge.nprb * ge.nprb : (long long)ge.ptheta * ge.nz * ge.n, flg, st,
+        rc = det_begin(h, ca, path != COLS_PLAIN, h->work[slot], total * N * N, f, prb, flg, st,
                        h->slot_max_ok[slot] ? h->slot_maxw + slot : nullptr, known_omax);
         if (rc) return rc;
     }
-    if (flg == 0) {
-        ca.dst = f; ca.aux = prb;
-        if (window) {
-            if constexpr (WinCfg<N>::fits) rc = launch_adjwin<N>(h, ca, st);
-        } else {
-            rc = launch_cols<N, +1, M_ADJ_OBJ>(h, ca, st);
-        }
-    } else {
-        ca.dst = prb; ca.aux = f;
-        if (window) {
-            if constexpr (WinCfg<N>::fits) rc = launch_gatherwin<N, M_ADJ_PRB>(h, ca, st);
-        } else {
-            rc = launch_cols<N, +1, M_ADJ_PRB>(h, ca, st);
-        }
-    }
+    rc = launch_adj_cols<N>(h, ca, flg, st, kCgSplit);
     if (!rc && h->deterministic) {
         if (finish < 0) h->det_pending = true;
-        else rc = det_end(h, flg == 0 ? f : prb, flg, st, finish);
+        else rc = det_end(h, f, prb, flg, st, finish);
     }
     return rc;
 }
@@ -119,9 +93,9 @@ int do_cg_rows(ptycho_handle h, RowFusedArgs a, hipStream_t st) {
     constexpr int C = ColCfg<N>::C;
     constexpr int B = 256 / Plan<N>::T;
     int strip0, nstrips;
-    strip_range<N>(h->ge, strip0, nstrips);
+    strip_range(h->ge, C, strip0, nstrips);
     a.table = h->table;
-    if (a.nrows <= 0) a.nrows = (long long)h->ge.ptheta * h->ge.nscan * N;   // preset: a range of positions (chunked line search)
+    if (a.nrows <= 0) a.nrows = h->ge.npos() * N;   // preset: a range of positions (chunked line search)
     a.xa = strip0 * C; a.xb = (strip0 + nstrips) * C;
     long long nb = (a.nrows + B - 1) / B;
     long long grid = nb < (long long)h->n_cu * 8 ? nb : (long long)h->n_cu * 8;
@@ -146,7 +120,7 @@ int do_cg_rows(ptycho_handle h, RowFusedArgs a, hipStream_t st) {
 template <int N>
 int do_cg_argmax(ptycho_handle h, int slot, unsigned long long* best, hipStream_t st, bool zeroed = false, int npos_limit = 0) {
     using CC = ColCfg<N>;
-    const int npos = npos_limit > 0 ? npos_limit : h->ge.ptheta * h->ge.nscan;
+    const int npos = npos_limit > 0 ? npos_limit : (int)h->ge.npos();
     constexpr int nstrips = N / CC::C;
     int ng = (h->n_cu * 8) / nstrips;
     if (ng < 1) ng = 1;
@@ -184,15 +158,10 @@ int launch_gatherwin_modes(ptycho_handle h, ColArgs a, hipStream_t st) {
 template <int N>
 int do_cg_fwd_cols_modes(ptycho_handle h, int nmodes, c32* const* dst, const c32* f, const float* scan, const c32* const* prbs,
                          int k_begin, int k_end, hipStream_t st, const double* skip) {
-    const Geom& ge = h->ge;
-    int strip0, nstrips;
-    strip_range<N>(h->ge, strip0, nstrips);
     int rc = sort_positions(h, scan, st);
     if (rc) return rc;
-    ColArgs ca{};
-    ca.src = f; ca.scan = scan; ca.table = h->table; ca.ge = ge; ca.order = h->order;
-    ca.k_begin = k_begin; ca.k_end = k_end; ca.strip0 = strip0; ca.nstrips = nstrips;
-    ca.skip = skip;
+    ColArgs ca = col_args(h, scan, k_begin, k_end, h->order, ColCfg<N>::C);
+    ca.src = f; ca.skip = skip;
     static const int nm_max = exp_env("PTYCHO_HIP_NMMAX", 4);   // comparison knob (2 / 1 modes per pass: profiles/r04/cfg3_experiments.txt)
     int k = 0;
     while (k < nmodes) {
@@ -213,15 +182,14 @@ int do_cg_fwd_cols_modes(ptycho_handle h, int nmodes, c32* const* dst, const c32
                 continue;
             }
         }
-        ca.aux = prbs[k]; ca.dst = dst[k];
-        if constexpr (WinCfg<N>::fits) {
-            rc = launch_gatherwin<N, M_FWD>(h, ca, st);
-        } else {
-            ColArgs cb = ca;
-            cb.order = nullptr;
-            if (k_begin != 0 || k_end != ge.ptheta * ge.nscan) return fail(PTYCHO_ERR_ARG, "position ranges need the windowed column pass (ndet <= 512)");
-            rc = launch_cols<N, -1, M_FWD>(h, cb, st);
+        // one mode: the single-probe pass, windowed wherever the window fits (as the passes above are, whatever option window says)
+        ColArgs cb = ca;
+        cb.aux = prbs[k]; cb.dst = dst[k];
+        if constexpr (!WinCfg<N>::fits) {
+            if (k_begin != 0 || k_end != h->ge.npos()) return fail(PTYCHO_ERR_ARG, "position ranges need the windowed column pass (ndet <= 512)");
+            cb.order = nullptr;   // k_cols<FWD> takes the positions as they come
         }
+        rc = launch_fwd_cols<N>(h, cb, st, kCgSplit, true);
         if (rc) return rc;
         ++k;
     }
@@ -240,7 +208,7 @@ int stats_stage(ptycho_handle h, int slot, const void* data, double* sums, int o
 int intensity_stage(ptycho_handle h, int nmodes, void* inten, const void* data, double* sums, hipStream_t st) {
     RowFusedArgs a{};
     for (int k = 0; k < nmodes; ++k) {
-        if (!slot_ready(h, slot_a(h, k))) return fail(PTYCHO_ERR_ARG, "work slot is empty");
+        if (int rc = need_slots(h, slot_a(h, k))) return rc;
         a.sm[k] = h->work[slot_a(h, k)];
     }
     a.nmodes = nmodes;
@@ -294,7 +262,7 @@ inline void ls_operands(RowFusedArgs& a, const void* data, const void* inten, co
 // sizes the pass that follows (single GPU); < 0: the caller all-reduces the costs and calls k_cg_ls_decide.
 int linesearch_stage(ptycho_handle h, int slot1, int slot2, const void* data, const LsSearch& s, hipStream_t st, int which = 0,
                      int decide_next = -1) {
-    if (!slot_ready(h, slot1) || !slot_ready(h, slot2)) return fail(PTYCHO_ERR_ARG, "work slot is empty");
+    if (int rc = need_slots(h, slot1, slot2)) return rc;
     RowFusedArgs a{};
     a.s1 = h->work[slot1]; a.s2 = h->work[slot2];
     ls_operands(a, data, nullptr, s);
@@ -311,7 +279,7 @@ int linesearch_stage(ptycho_handle h, int slot1, int slot2, const void* data, co
 int linesearch_modes_stage(ptycho_handle h, int mode0, int nmodes, const void* data, const void* inten, const LsSearch& s, hipStream_t st) {
     RowFusedArgs a{};
     for (int k = 0; k < nmodes; ++k) {
-        if (!slot_ready(h, slot_a(h, mode0 + k)) || !slot_ready(h, slot_b(h, mode0 + k))) return fail(PTYCHO_ERR_ARG, "work slot is empty");
+        if (int rc = need_slots(h, slot_a(h, mode0 + k), slot_b(h, mode0 + k))) return rc;
         a.sm[2 * k] = h->work[slot_a(h, mode0 + k)];
         a.sm[2 * k + 1] = h->work[slot_b(h, mode0 + k)];
     }
@@ -323,14 +291,14 @@ int linesearch_modes_stage(ptycho_handle h, int mode0, int nmodes, const void* d
 // ... and all modes of one chunk of positions in the compact slot layout (mode k of the chunk at tile k * pc of the shared slot)
 int linesearch_chunk_stage(ptycho_handle h, int chunk, const void* data, const LsSearch& s, hipStream_t st) {
     const int M = h->compact_modes;
-    const long long total = (long long)h->ge.ptheta * h->ge.nscan;
+    const long long total = h->ge.npos();
     const long long pc = (total + h->sort_chunks - 1) / h->sort_chunks;
     const long long p0 = chunk * pc, p1 = (chunk + 1) * pc < total ? (chunk + 1) * pc : total;
     if (p1 <= p0) return PTYCHO_OK;
     const size_t tile = (size_t)h->ge.ndet * h->ge.ndet;
     RowFusedArgs a{};
     for (int k = 0; k < M; ++k) {
-        if (!slot_ready(h, slot_a(h, k)) || !slot_ready(h, slot_b(h, 0))) return fail(PTYCHO_ERR_ARG, "work slot is empty");
+        if (int rc = need_slots(h, slot_a(h, k), slot_b(h, 0))) return rc;
         a.sm[2 * k] = h->work[slot_a(h, k)] + (size_t)p0 * tile;
         a.sm[2 * k + 1] = h->work[slot_b(h, 0)] + (size_t)k * pc * tile;
     }
@@ -345,7 +313,7 @@ int linesearch_chunk_stage(ptycho_handle h, int chunk, const void* data, const L
 // pass that follows finds its peaks cleared
 int cross_stage(ptycho_handle h, int slot1, int slot2, c32* image_product, double gamma, const double* gamma_dev, hipStream_t st,
                 bool angle0 = false) {
-    if (!slot_ready(h, slot1) || !slot_ready(h, slot2)) return fail(PTYCHO_ERR_ARG, "work slot is empty");
+    if (int rc = need_slots(h, slot1, slot2)) return rc;
     RowFusedArgs a{};
     a.s1 = h->work[slot1]; a.s2 = h->work[slot2]; a.out = h->work[slot2]; a.ip = image_product;
     a.gamma0 = (float)gamma; a.gamma_dev = gamma_dev;
@@ -379,7 +347,7 @@ int zoom_impl(ptycho_handle h, const void* image_product, const void* best, cons
     int rc = check_args(h);
     if (rc) return rc;
     if (!image_product) {   // NULL: work slot 2 (see cross_public)
-        if (!slot_ready(h, 2)) return fail(PTYCHO_ERR_ARG, "work slot is empty");
+        if ((rc = need_slots(h, 2))) return rc;
         image_product = h->work[2];
     }
     if (!best || !vt || !lz || !shifts) return fail(PTYCHO_ERR_ARG, "null operand");
@@ -388,7 +356,7 @@ int zoom_impl(ptycho_handle h, const void* image_product, const void* best, cons
     if (N % 16 != 0 || N > 1024) return fail(PTYCHO_ERR_ARG, "zoomed DFT kernel needs ndet %% 16 == 0 and ndet <= 1024");
     if (ups < 1 || ups > nthreads || nc < 0 || nc > kZoomRK || !(upsample_factor >= 1.0))
         return fail(PTYCHO_ERR_ARG, "zoomed DFT window, rank split or upsample factor out of range");
-    const int npos_all = h->ge.ptheta * h->ge.nscan;
+    const int npos_all = (int)h->ge.npos();
     const int npos = npos_limit > 0 ? npos_limit : npos_all;
     hipStream_t st = (hipStream_t)stream;
     if (!h->zoom_phase) {   // px, py: complex128 [npos][N] each; coarse shifts: float64 [npos][2]
@@ -437,7 +405,7 @@ template <int N>
 int do_fwd_cols_pair(ptycho_handle h, int slot_p, int slot_o, const c32* f, const float* scan, const c32* prb, const c32* ones, hipStream_t st) {
     c32* dst[2] = {h->work[slot_p], h->work[slot_o]};
     const c32* pr[2] = {prb, ones};
-    return do_cg_fwd_cols_modes<N>(h, 2, dst, f, scan, pr, 0, h->ge.ptheta * h->ge.nscan, st, nullptr);
+    return do_cg_fwd_cols_modes<N>(h, 2, dst, f, scan, pr, 0, (int)h->ge.npos(), st, nullptr);
 }
 int fwd_cols_pair(ptycho_handle h, int slot_p, int slot_o, const void* f, const void* scan, const void* prb, const void* ones, hipStream_t st) {
     int rc = ensure_work(h, slot_p);
@@ -461,7 +429,7 @@ int grad_stage(ptycho_handle h, void* f, const void* scan, void* prb, int flg, c
     const Geom& ge = h->ge;
     const bool det = det_fixed_point(h);
     if (!det) {   // float atomics accumulate into the gradient
-        const size_t n = flg == 0 ? (size_t)ge.ptheta * ge.nz * ge.n : (size_t)ge.ptheta * ge.nprb * ge.nprb;
+        const size_t n = flg == 0 ? (size_t)ge.obj_elems() : (size_t)ge.prb_elems();
         HIP_TRY(hipMemsetAsync(flg == 0 ? f : prb, 0, n * sizeof(c32), st));
     }
     return adj_cols_stage(h, 1, f, scan, prb, flg, known_omax, det ? (h->defer_finish ? -1 : 0) : 1, st);
@@ -480,6 +448,116 @@ void dy_direction(ptycho_handle h, double* state, int which, int first, void* gr
                        state, which);
 }
 
+// x += gamma d with gamma on the device (state word)
+int axpy_state(ptycho_handle h, void* x, const void* d, long long n, const double* gamma, hipStream_t st) {
+    hipLaunchKernelGGL(k_cg_axpy, dim3(small_grid(h, n)), dim3(256), 0, st, (c32*)x, (const c32*)d, n, gamma);
+    HIP_TRY(hipGetLastError());
+    return PTYCHO_OK;
+}
+
+// ---- bodies of the native stage entry points (ptycho_cg_obj_* / prb_* / ls_*), behind their argument checks ----
+int obj_begin_native(ptycho_handle h, double* state, const void* psi, const void* scan, const void* prb, const void* ones_prb,
+                     const void* data, hipStream_t st) {
+    h->native_order = 1;   // the native loop keeps track of scan itself (ptycho_cg_obj_finish invalidates the order)
+    h->det_pending = false;
+    int rc = ones_prb ? fwd_cols_pair(h, 0, 2, psi, scan, prb, ones_prb, st)   // + slot 2 <- column pass of fwd(psi, 1)
+                      : fwd_cols_stage(h, 0, psi, scan, prb, st);
+    if (rc) return rc;
+    return stats_stage(h, 0, data, state + PTYCHO_ST_A, 1, st);
+}
+
+int obj_grad_native(ptycho_handle h, double* state, const void* scan, void* prb, const void* data, void* grad, hipStream_t st) {
+    // probe *= a / b (ptycho.py:344) and max |probe| (the gradient normalisation of :356 and the fixed-point scale) in one pass
+    launch_absmax(h, (const c32*)prb, h->ge.prb_elems(), 4, state + PTYCHO_ST_MAX_PRB, state + PTYCHO_ST_A, st);
+    h->max_prb_valid = true;
+    int rc = project_stage(h, 0, 1, data, nullptr, state + PTYCHO_ST_A, 0, state + PTYCHO_ST_COST, 1, st);
+    if (rc) return rc;
+    return grad_stage(h, grad, scan, prb, 0, state + PTYCHO_ST_MAX_PRB, st);
+}
+
+int obj_dir_native(ptycho_handle h, double* state, int first, const void* scan, const void* prb, const void* ones_prb, const void* data,
+                   void* grad, void* grad0, void* dpsi, hipStream_t st) {
+    if (!h->max_prb_valid) launch_absmax(h, (const c32*)prb, h->ge.prb_elems(), 4, state + PTYCHO_ST_MAX_PRB, nullptr, st);
+    h->max_prb_valid = false;
+    dy_direction(h, state, 0, first, grad, grad0, dpsi, h->ge.obj_elems(), 0.0f, 0.0f, st);
+    int rc = ones_prb ? fwd_cols_pair(h, 1, 3, dpsi, scan, prb, ones_prb, st)   // + slot 3 <- column pass of fwd(dpsi, 1)
+                      : fwd_cols_stage(h, 1, dpsi, scan, prb, st);
+    if (rc) return rc;
+    return ls_pass(h, data, 1, state, st, 0, h->ls_fused_decide ? kLsNext[1] : -1);
+}
+
+int ls_begin_native(double* state, int which, hipStream_t st) {
+    hipLaunchKernelGGL(k_cg_ls_begin, dim3(1), dim3(1), 0, st, state, which);
+    HIP_TRY(hipGetLastError());
+    return PTYCHO_OK;
+}
+int ls_decide_native(double* state, int which, int next_groups, hipStream_t st) {
+    hipLaunchKernelGGL(k_cg_ls_decide, dim3(1), dim3(1), 0, st, state, which,
+                       which == 0 ? (int)PTYCHO_ST_GAMMA_PSI : (int)PTYCHO_ST_GAMMA_PRB, next_groups);
+    HIP_TRY(hipGetLastError());
+    return PTYCHO_OK;
+}
+int ls_next_native(ptycho_handle h, double* state, int which, int pass, const void* data, int use_ab, hipStream_t st) {
+    if (h->ls_fused_decide) {
+        // the pass before this call has decided on its own totals and sized this one: just issue it
+        if (pass > 3) return pass == 4 ? (int)PTYCHO_OK : fail(PTYCHO_ERR_ARG, "option ls_fused_decide: passes 1, 2, 3, 4 only");
+        return ls_pass(h, data, use_ab, state, st, which, kLsNext[pass + 1]);
+    }
+    int rc = ls_decide_native(state, which, kLsNext[pass], st);
+    if (rc || pass == 4) return rc;
+    return ls_pass(h, data, use_ab, state, st, which, -1);
+}
+
+// psi += gamma dpsi, after the position correction of angle 0 (ptycho.py:399-403) where it is asked for
+int obj_finish_native(ptycho_handle h, double* state, int correct_positions, void* psi, const void* dpsi, void* scan, const void* ones_prb,
+                      const void* vt, const void* lz, int nc, int ups, double upsample_factor, hipStream_t st) {
+    const Geom& ge = h->ge;
+    if (correct_positions) {
+        if (!ones_prb || !vt || !lz) return fail(PTYCHO_ERR_ARG, "null operand");
+        const size_t npos = (size_t)ge.nscan;
+        if (!h->reg_ip) {
+            HIP_TRY(hipMalloc((void**)&h->reg_ip, npos * ge.ndet * ge.ndet * sizeof(c32)));
+            HIP_TRY(hipMalloc((void**)&h->reg_best, npos * sizeof(unsigned long long)));
+            HIP_TRY(hipMalloc((void**)&h->reg_shifts, npos * 2 * sizeof(double)));
+        }
+        // ptycho.py:399-402: tmp1 = fwd(psi, 1), tmp2 = fwd(psi + gamma dpsi, 1) = tmp1 + gamma fwd(dpsi, 1)
+        // 2: ptycho_cg_reg_prepare (or ptycho_cg_obj_begin2) left the column pass of tmp1 in slot 2;
+        // 3: and ptycho_cg_obj_dir2 the column pass of fwd(dpsi, 1) in slot 3
+        const int s1 = correct_positions >= 2 ? 2 : 0, s2 = correct_positions == 3 ? 3 : 1;
+        int rc = s1 == 0 ? fwd_cols_stage(h, 0, psi, scan, ones_prb, st, ge.nscan) : (int)PTYCHO_OK;
+        if (!rc && s2 == 1) rc = fwd_cols_stage(h, 1, dpsi, scan, ones_prb, st, ge.nscan);
+        if (!rc) rc = cross_stage(h, s1, s2, h->reg_ip, 0.0, state + PTYCHO_ST_GAMMA_PSI, st, true);
+        if (!rc) rc = argmax_stage(h, s2, h->reg_best, st, true, ge.nscan);
+        // the kernel that finds the shifts also adds them to scan[0, :] (ptycho.py:403)
+        if (!rc) rc = zoom_impl(h, h->reg_ip, h->reg_best, vt, lz, nc, ups, upsample_factor, h->reg_shifts, (float*)scan, st, ge.nscan);
+        if (rc) return rc;
+        h->order_scan = nullptr;   // the positions moved: the next column pass sorts again
+    }
+    return axpy_state(h, psi, dpsi, ge.obj_elems(), state + PTYCHO_ST_GAMMA_PSI, st);
+}
+
+int prb_grad_native(ptycho_handle h, double* state, const void* psi, const void* scan, const void* prb, const void* data, void* gprb,
+                    hipStream_t st) {
+    int rc = fwd_cols_stage(h, 0, psi, scan, prb, st);
+    if (rc) return rc;
+    // max |psi|: the gradient normalisation of ptycho.py:431 and the fixed-point scale of the probe adjoint
+    launch_absmax(h, (const c32*)psi, h->ge.obj_elems(), 4, state + PTYCHO_ST_MAX_PSI, nullptr, st);
+    h->max_psi_valid = true;
+    rc = project_stage(h, 0, 1, data, nullptr, nullptr, 0, state + PTYCHO_ST_COST2, 1, st);
+    if (rc) return rc;
+    return grad_stage(h, (void*)psi, scan, gprb, 1, state + PTYCHO_ST_MAX_PSI, st);
+}
+
+int prb_dir_native(ptycho_handle h, double* state, int first, double nscan_total, double nmodes, const void* psi, const void* scan,
+                   const void* data, void* gprb, void* gprb0, void* dprb, hipStream_t st) {
+    if (!h->max_psi_valid) launch_absmax(h, (const c32*)psi, h->ge.obj_elems(), 4, state + PTYCHO_ST_MAX_PSI, nullptr, st);
+    h->max_psi_valid = false;
+    dy_direction(h, state, 1, first, gprb, gprb0, dprb, h->ge.prb_elems(), (float)nscan_total, (float)nmodes, st);
+    int rc = fwd_cols_stage(h, 1, psi, scan, dprb, st);
+    if (rc) return rc;
+    return ls_pass(h, data, 0, state, st, 1, h->ls_fused_decide ? kLsNext[1] : -1);
+}
+
 // ---- several probe modes per column pass; compact slot layout with a chunked line search ----
 
 int fwd_cols_modes_impl(ptycho_handle h, int nmodes, int mode0, const void* f, const void* scan,
@@ -487,7 +565,7 @@ int fwd_cols_modes_impl(ptycho_handle h, int nmodes, int mode0, const void* f, c
     int rc = check_args(h);
     if (rc) return rc;
     if (!f || !scan || !prbs || nmodes < 1 || mode0 < 0 || mode0 + nmodes > kMaxModes) return fail(PTYCHO_ERR_ARG, "bad operand");
-    const long long total = (long long)h->ge.ptheta * h->ge.nscan;
+    const long long total = h->ge.npos();
     const size_t tile = (size_t)h->ge.ndet * h->ge.ndet;
     c32* dst[kMaxModes];
     const c32* pr[kMaxModes];
@@ -516,6 +594,15 @@ int fwd_cols_modes_impl(ptycho_handle h, int nmodes, int mode0, const void* f, c
     PTY_DISPATCH(h->ge.ndet, (do_cg_fwd_cols_modes<NN>(h, nmodes, dst, (const c32*)f, (const float*)scan, pr, k_begin, k_end, st, skip)));
 }
 
+// body of ptycho_cg_ls_obj_chunk: direction column passes of this chunk, all modes side by side in the shared slot (skipped
+// once the search is resolved), then their line-search pass; the chunks of one pass accumulate, the first one stores
+int ls_obj_chunk_native(ptycho_handle h, double* state, int chunk, const void* dpsi, const void* scan, const void* const* prbs,
+                        const void* data, const double* ab, void* stream) {
+    int rc = fwd_cols_modes_impl(h, h->compact_modes, 0, dpsi, scan, prbs, 1, chunk, stream, state + PTYCHO_ST_LS_RESOLVED);
+    if (rc) return rc;
+    return linesearch_chunk_stage(h, chunk, data, ls_on_state(state, ab, chunk == 0 ? 1 : 0), (hipStream_t)stream);
+}
+
 // ---- orthogonal probe modes (k_modes.hpp): no handle ----
 template <int M>
 int do_orthogonalize_modes(c32* const* x, int narr, int ptheta, long long npix, double* v, double* powers, hipStream_t st) {
@@ -532,6 +619,14 @@ int do_orthogonalize_modes(c32* const* x, int narr, int ptheta, long long npix, 
         HIP_TRY(hipGetLastError());
     }
     return PTYCHO_OK;
+}
+// nmodes in [1, kOrthoMaxModes] (the caller checked) to the template argument, every case named once
+template <int M = 1>
+int orthogonalize_modes(int nmodes, c32* const* x, int narr, int ptheta, long long npix, double* v, double* powers, hipStream_t st) {
+    if constexpr (M < kOrthoMaxModes) {
+        if (nmodes != M) return orthogonalize_modes<M + 1>(nmodes, x, narr, ptheta, npix, v, powers, st);
+    }
+    return do_orthogonalize_modes<M>(x, narr, ptheta, npix, v, powers, st);
 }
 
 }  // namespace

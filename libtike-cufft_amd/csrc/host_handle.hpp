@@ -140,6 +140,11 @@ int check_stage(ptycho_handle h, const double* state, const P*... operands) {
     return check_args(h, operands...);
 }
 
+// argument checks that several entry points share
+inline int check_flg(int flg) { return flg == 0 || flg == 1 ? (int)PTYCHO_OK : fail(PTYCHO_ERR_ARG, "flg must be 0 (object) or 1 (probe)"); }
+inline int check_which(int which) { return which == 0 || which == 1 ? (int)PTYCHO_OK : fail(PTYCHO_ERR_ARG, "which must be 0 (object) or 1 (probe)"); }
+inline int check_ncand(int ncand) { return ncand >= 1 && ncand <= kMaxCand ? (int)PTYCHO_OK : fail(PTYCHO_ERR_ARG, "ncand must be in [1, 16]"); }
+
 struct ProfSpan {   // brackets one launch with events when profiling is on
     ptycho_handle h;
     hipStream_t st;
@@ -171,7 +176,7 @@ int alloc_scratch(ptycho_handle h) {
         HIP_TRY(hipFree(h->scratch));
         h->scratch = nullptr;
     }
-    const long long total = (long long)h->ge.ptheta * h->ge.nscan;
+    const long long total = h->ge.npos();
     long long c = h->chunk < total ? h->chunk : total;
     if (c < 1) c = 1;
     HIP_TRY(hipMalloc((void**)&h->scratch, (size_t)c * h->ge.ndet * h->ge.ndet * sizeof(c32)));
@@ -186,7 +191,7 @@ int free_scratch(ptycho_handle h) {   // options "chunk" and "release_scratch": 
 
 // processing order of the windowed column passes: (angle, column bucket, row), one ranking launch (k_rank_positions)
 int sort_positions(ptycho_handle h, const float* scan, hipStream_t st) {
-    const int total = h->ge.ptheta * h->ge.nscan;
+    const int total = (int)h->ge.npos();
     // The order depends only on the scan positions.  A caller that knows they have not
     // changed since the previous call on this handle (option "trust_order") skips the sort.
     if ((h->trust_order || h->native_order) && h->order_scan == scan) return PTYCHO_OK;
@@ -206,7 +211,7 @@ int sort_positions(ptycho_handle h, const float* scan, hipStream_t st) {
 }
 
 int alloc_sort(ptycho_handle h) {
-    const size_t total = (size_t)h->ge.ptheta * h->ge.nscan;
+    const size_t total = (size_t)h->ge.npos();
     const size_t nwords = total + (total + 255) / 256;
     HIP_TRY(hipMalloc((void**)&h->order, total * sizeof(int)));
     HIP_TRY(hipMalloc((void**)&h->sort_counts, nwords * sizeof(int)));

@@ -124,18 +124,77 @@ int launch_rows_split(ptycho_handle h, RowArgs a, hipStream_t st) {
     return PTYCHO_OK;
 }
 
-template <int N>
-void strip_range(const Geom& ge, int& strip0, int& nstrips) {
-    constexpr int C = ColCfg<N>::C;
+// the strips of C detector columns that the probe touches
+inline void strip_range(const Geom& ge, int C, int& strip0, int& nstrips) {
     strip0 = ge.pad / C;
     const int last = (ge.pad + ge.nprb - 1) / C;
     nstrips = last - strip0 + 1;
 }
 
+// ---- the column pass of an operator or a CG stage: the path (col_path.hpp), its arguments, one launcher per direction ----
+// force_window: the multi-mode forward stage is windowed wherever the window fits, whatever option window says
+template <int N>
+ColPath col_path_for(ptycho_handle h, ColMode mode, bool allow_split, bool force_window = false) {
+    return col_path(N, WinCfg<N>::fits, h->use_window || force_window, h->use_split, allow_split, mode);
+}
+
+// what every column launch shares: table, geometry, positions and their order (nullptr: as they come), range of positions,
+// strips of C columns
+ColArgs col_args(ptycho_handle h, const float* scan, long long k_begin, long long k_end, const int* order, int C) {
+    ColArgs ca{};
+    ca.scan = scan; ca.table = h->table; ca.ge = h->ge; ca.order = order;
+    ca.k_begin = (int)k_begin; ca.k_end = (int)k_end;
+    strip_range(h->ge, C, ca.strip0, ca.nstrips);
+    return ca;
+}
+template <int N>
+ColArgs col_args(ptycho_handle h, const float* scan, long long k_begin, long long k_end, ColPath p, ColMode mode) {
+    return col_args(h, scan, k_begin, k_end, col_path_sorts(p, mode) ? h->order : nullptr, col_strip_width(p, mode, ColCfg<N>::C));
+}
+
+// The if constexpr guards keep kernels that do not exist (no window at 1024 / 2048, split at 256 only) from being instantiated.
+template <int N>
+int launch_fwd_cols(ptycho_handle h, const ColArgs& ca, hipStream_t st, bool allow_split, bool force_window = false) {
+    switch (col_path_for<N>(h, COL_FWD, allow_split, force_window)) {
+        case COLS_PLAIN: return launch_cols<N, -1, M_FWD>(h, ca, st);
+        case COLS_GATHERWIN:
+            if constexpr (WinCfg<N>::fits) return launch_gatherwin<N, M_FWD>(h, ca, st);
+            break;
+        case COLS_GATHERWIN_SPLIT:
+            // exactly one resident round of workgroups (two per CU), runs of 64 positions at 4096: 0.42 -> 0.395 ms against
+            // two rounds of shorter runs; 1.5 or 3 rounds (a ragged tail) cost 10-20 % (profiles/r03/knob_sweep.txt)
+            if constexpr (N == 256) return launch_gatherwin<N, M_FWD, true, kSplitFwdC>(h, ca, st, h->n_cu * 2);
+            break;
+        default: break;
+    }
+    return fail(PTYCHO_ERR_ARG, "internal: no forward column pass for this path");
+}
+
+template <int N>
+int launch_adj_cols(ptycho_handle h, const ColArgs& ca, int flg, hipStream_t st, bool allow_split) {
+    switch (col_path_for<N>(h, flg == 0 ? COL_ADJ_OBJ : COL_ADJ_PRB, allow_split)) {
+        case COLS_PLAIN: return flg == 0 ? launch_cols<N, +1, M_ADJ_OBJ>(h, ca, st) : launch_cols<N, +1, M_ADJ_PRB>(h, ca, st);
+        case COLS_ADJWIN:
+        case COLS_ADJREG:   // launch_adjwin picks k_cols_adjreg at 256 and 512
+            if constexpr (WinCfg<N>::fits) return launch_adjwin<N>(h, ca, st);
+            break;
+        case COLS_GATHERWIN:
+            if constexpr (WinCfg<N>::fits) return launch_gatherwin<N, M_ADJ_PRB>(h, ca, st);
+            break;
+        case COLS_ADJREG_SPLIT:
+            if constexpr (N == 256) return launch_adjwin<N, true>(h, ca, st);
+            break;
+        case COLS_GATHERWIN_SPLIT:
+            if constexpr (N == 256) return launch_gatherwin<N, M_ADJ_PRB, true>(h, ca, st);
+            break;
+    }
+    return fail(PTYCHO_ERR_ARG, "internal: no adjoint column pass for this path");
+}
+
 #ifdef PTYCHO_EXPERIMENTS
 int do_fwd_fused(ptycho_handle h, c32* g, const c32* f, const float* scan, const c32* prb, hipStream_t st) {
     const Geom& ge = h->ge;
-    const int total = ge.ptheta * ge.nscan;
+    const int total = (int)ge.npos();
     const int N = ge.ndet;
     if (!h->prbp) HIP_TRY(hipMalloc((void**)&h->prbp, (size_t)ge.ptheta * N * N * sizeof(c32)));
     // positions in sorted order: the workgroups in flight then touch neighbouring object rows (L2 hits)
@@ -175,7 +234,7 @@ int launch_fwd_tile(ptycho_handle h, c32* g, const c32* f, const float* scan, co
     const Geom& ge = h->ge;
     TileArgs ta{};
     ta.obj = f; ta.prb = prb; ta.g = g; ta.scan = scan; ta.table = h->table; ta.ge = ge;
-    ta.npos = (int)((long long)ge.ptheta * ge.nscan);
+    ta.npos = (int)(ge.npos());
     {
         ProfSpan ps(h, K_TILE_FWD, st);
         hipLaunchKernelGGL((k_fwd_tile<N>), dim3(tile_grid<N>(h, ta.npos)), dim3(TileCfg<N>::NT), 0, st, ta);
@@ -188,7 +247,7 @@ int launch_adjprb_tile(ptycho_handle h, c32* prb_out, const c32* g, const float*
     const Geom& ge = h->ge;
     TileArgs ta{};
     ta.obj = f; ta.g = const_cast<c32*>(g); ta.out = prb_out; ta.scan = scan; ta.table = h->table; ta.ge = ge;
-    ta.npos = (int)((long long)ge.ptheta * ge.nscan);
+    ta.npos = (int)(ge.npos());
     {
         ProfSpan ps(h, K_TILE_ADJ_PRB, st);
                 // every workgroup ends with one atomic pair per probe pixel, all on the same ndet^2 addresses: few, long-running
@@ -213,11 +272,18 @@ void launch_absmax(ptycho_handle h, const c32* x, long long n, int per_cu, doubl
 }
 // do the adjoints of the native CG stages run in fixed point?  (the windowed kernels carry the integer atomics)
 inline bool det_fixed_point(ptycho_handle h) { return h->deterministic && h->use_window && h->ge.ndet <= 512; }
-int det_begin(ptycho_handle h, ColArgs& ca, const c32* gsrc, long long gcount, const c32* other, long long ocount, int flg, hipStream_t st,
+// windowed: the column pass about to run carries the integer atomics; the operand that is not written (probe for the object
+// adjoint, object for the probe adjoint) scales the fixed point beside gsrc
+int det_begin(ptycho_handle h, ColArgs& ca, bool windowed, const c32* gsrc, long long gcount, const c32* f, const c32* prb, int flg, hipStream_t st,
               const double* known_gmax = nullptr,   // max |gsrc| / max |other| are already on the device (k_cg_absmax format)
               const double* known_omax = nullptr) {
     const Geom& ge = h->ge;
-    const size_t nobj = (size_t)ge.ptheta * ge.nz * ge.n, nprb = (size_t)ge.ptheta * ge.nprb * ge.nprb;
+    if (!windowed)
+        return fail(PTYCHO_ERR_ARG, h->bs_m ? "option deterministic needs the windowed object adjoint (option window, nprb <= ~1000)"
+                                            : "option deterministic needs the windowed adjoint kernels (ndet <= 512)");
+    const c32* other = flg == 0 ? prb : f;
+    const long long ocount = flg == 0 ? ge.prb_elems() : ge.obj_elems();
+    const size_t nobj = (size_t)ge.obj_elems(), nprb = (size_t)ge.prb_elems();
     // option "defer_finish": a gradient that ptycho_cg_obj_grad / prb_grad left in the fixed-point image has not been
     // folded in yet (ptycho_cg_obj_dir / prb_dir do that); another deterministic adjoint would add into the same image
     if (h->det_pending)
@@ -242,9 +308,9 @@ int det_begin(ptycho_handle h, ColArgs& ca, const c32* gsrc, long long gcount, c
     ca.det = h->last_det;
     return PTYCHO_OK;
 }
-int det_end(ptycho_handle h, c32* dst, int flg, hipStream_t st, int add = 1) {
-    const Geom& ge = h->ge;
-    const long long n = flg == 0 ? (long long)ge.ptheta * ge.nz * ge.n : (long long)ge.ptheta * ge.nprb * ge.nprb;
+int det_end(ptycho_handle h, c32* f, c32* prb, int flg, hipStream_t st, int add = 1) {
+    c32* dst = flg == 0 ? f : prb;
+    const long long n = flg == 0 ? h->ge.obj_elems() : h->ge.prb_elems();
     long long g = (n + 255) / 256;
     if (g > (long long)h->n_cu * 4) g = (long long)h->n_cu * 4;
     hipLaunchKernelGGL(k_det_finish, dim3((unsigned)g), dim3(256), 0, st, dst, h->det_acc, n, h->last_det, add);
@@ -261,13 +327,7 @@ inline unsigned small_grid(ptycho_handle h, long long n) {
 
 template <int N>
 int do_fwd(ptycho_handle h, c32* g, const c32* f, const float* scan, const c32* prb, hipStream_t st) {
-    constexpr int C = ColCfg<N>::C;
     const Geom& ge = h->ge;
-    const long long total = (long long)ge.ptheta * ge.nscan;
-    int strip0, nstrips;
-    strip_range<N>(ge, strip0, nstrips);
-    const bool window = h->use_window && WinCfg<N>::fits;
-    int rc = PTYCHO_OK;
     if constexpr (N <= 128) {
         // the tile fits one CU's LDS: one launch, no intermediate in HBM, no position sort (16-byte rows of g)
         if (h->use_tile && ((size_t)g % 16) == 0 && ge.n >= 2 && (long long)ge.nz * ge.n < (1ll << 28)) return launch_fwd_tile<N>(h, g, f, scan, prb, st);
@@ -278,41 +338,23 @@ int do_fwd(ptycho_handle h, c32* g, const c32* f, const float* scan, const c32* 
         if (h->use_fused && ge.n % 2 == 0 && ((size_t)f % 16) == 0) return do_fwd_fused(h, g, f, scan, prb, st);
     }
 #endif
-    if (window) {
-        rc = sort_positions(h, scan, st);
-        if (rc) return rc;
-    }
+    const ColPath path = col_path_for<N>(h, COL_FWD, true);
+    int rc = col_path_sorts(path, COL_FWD) ? sort_positions(h, scan, st) : (int)PTYCHO_OK;
+    if (rc) return rc;
     // The column pass writes straight into g and the row pass transforms g in place, so the
     // forward operator needs no scratch and is issued as one launch pair over all positions.
-    ColArgs ca{};
-    ca.src = f; ca.dst = g; ca.aux = prb; ca.scan = scan; ca.table = h->table; ca.ge = ge;
-    ca.k_begin = 0; ca.k_end = (int)total; ca.strip0 = strip0; ca.nstrips = nstrips;
+    ColArgs ca = col_args<N>(h, scan, 0, ge.npos(), path, COL_FWD);
+    ca.src = f; ca.dst = g; ca.aux = prb;
+    // the row pass's column limits follow the strips (32 columns wide where the pass is split)
+    const int C = col_strip_width(path, COL_FWD, ColCfg<N>::C);
     RowArgs ra{};
     ra.src = g; ra.dst = g; ra.table = h->table; ra.tile_index = nullptr;
-    ra.nrows = total * N; ra.xa = strip0 * C; ra.xb = (strip0 + nstrips) * C; ra.wa = 0; ra.wb = N;
-    if constexpr (N == 256) {
-        if (window && h->use_split) {
-            // 32-column strips: the strip range and the row pass's column limits follow the wider strips
-            constexpr int CF = 32;
-            ca.order = h->order;
-            ca.strip0 = ge.pad / CF;
-            ca.nstrips = (ge.pad + ge.nprb - 1) / CF - ca.strip0 + 1;
-            ra.xa = ca.strip0 * CF; ra.xb = (ca.strip0 + ca.nstrips) * CF;
-            // exactly one resident round of workgroups (two per CU), runs of 64 positions at 4096: 0.42 -> 0.395 ms against
-            // two rounds of shorter runs; 1.5 or 3 rounds (a ragged tail) cost 10-20 % (profiles/r03/knob_sweep.txt)
-            rc = launch_gatherwin<N, M_FWD, true, CF>(h, ca, st, h->n_cu * 2);
-            if (rc) return rc;
-            return launch_rows_split<N, -1>(h, ra, st);
-        }
-    }
-    if (window) {
-        ca.order = h->order;
-        if constexpr (WinCfg<N>::fits) rc = launch_gatherwin<N, M_FWD>(h, ca, st);
-    } else {
-        ca.order = nullptr;
-        rc = launch_cols<N, -1, M_FWD>(h, ca, st);
-    }
+    ra.nrows = ge.npos() * N; ra.xa = ca.strip0 * C; ra.xb = (ca.strip0 + ca.nstrips) * C; ra.wa = 0; ra.wb = N;
+    rc = launch_fwd_cols<N>(h, ca, st, true);
     if (rc) return rc;
+    if constexpr (N == 256) {
+        if (col_path_split(path)) return launch_rows_split<N, -1>(h, ra, st);
+    }
     return launch_rows<N, -1>(h, ra, st);
 }
 
@@ -320,10 +362,10 @@ template <int N>
 int do_adj(ptycho_handle h, c32* f, const c32* g, const float* scan, c32* prb, int flg, hipStream_t st) {
     constexpr int C = ColCfg<N>::C;
     const Geom& ge = h->ge;
-    const long long total = (long long)ge.ptheta * ge.nscan;
-    int strip0, nstrips;
-    strip_range<N>(ge, strip0, nstrips);
-    const bool window = flg == 0 && h->use_window && WinCfg<N>::fits;
+    const long long total = ge.npos();
+    const ColMode mode = flg == 0 ? COL_ADJ_OBJ : COL_ADJ_PRB;
+    const ColPath path = col_path_for<N>(h, mode, true);
+    const RowPath rows = row_path(N, path, mode, h->use_tile, aligned16(g));
     if constexpr (N <= 128) {
         // probe adjoint with the tile in LDS: one launch, g read once, no scratch, no position sort
         if (flg == 1 && h->use_tile && !h->deterministic && ((size_t)g % 16) == 0 && (long long)ge.nz * ge.n < (1ll << 28))
@@ -339,24 +381,23 @@ int do_adj(ptycho_handle h, c32* f, const c32* g, const float* scan, c32* prb, i
     }
     ColArgs det{};
     if (h->deterministic) {
-        if (!(h->use_window && WinCfg<N>::fits)) return fail(PTYCHO_ERR_ARG, "option deterministic needs the windowed adjoint kernels (ndet <= 512)");
-        rc = det_begin(h, det, g, total * N * N, flg == 0 ? prb : f, flg == 0 ? (long long)ge.ptheta * ge.nprb * ge.nprb : (long long)ge.ptheta * ge.nz * ge.n, flg, st);
+        rc = det_begin(h, det, path != COLS_PLAIN, g, total * N * N, f, prb, flg, st);
         if (rc) return rc;
     }
     for (long long k0 = 0; k0 < total; k0 += h->chunk) {
         const long long k1 = k0 + h->chunk < total ? k0 + h->chunk : total;
+        ColArgs ca = col_args<N>(h, scan, k0, k1, path, mode);
+        ca.src = h->scratch; ca.dst = flg == 0 ? f : prb; ca.aux = flg == 0 ? prb : f;
+        ca.det_acc = det.det_acc; ca.det = det.det;
         RowArgs ra{};
         ra.src = g; ra.dst = h->scratch; ra.table = h->table; ra.tile_index = h->order + k0;
-        ra.nrows = (k1 - k0) * N; ra.xa = 0; ra.xb = N; ra.wa = strip0 * C; ra.wb = (strip0 + nstrips) * C;
-        bool split = false, tiled = false;
-        if constexpr (N == 256) split = h->use_split && h->use_window;
+        ra.nrows = (k1 - k0) * N; ra.xa = 0; ra.xb = N; ra.wa = ca.strip0 * C; ra.wb = (ca.strip0 + ca.nstrips) * C;
         if constexpr (N == 256) {
-            if (split) rc = launch_rows_split<N, +1>(h, ra, st);
+            if (rows == ROWS_SPLIT) rc = launch_rows_split<N, +1>(h, ra, st);
         }
         if constexpr (N <= 128) {
             // whole tiles through LDS, 16 bytes per lane (k_tile.hpp): 0.34 -> 0.047 ms at 16384 x 32^2
-            tiled = h->use_tile && ((size_t)g % 16) == 0;
-            if (tiled) {
+            if (rows == ROWS_TILE || rows == ROWS_SLAB) {
                 ProfSpan ps(h, K_ROWS_INV, st);
                 if constexpr (!is_pow2(N) && N >= 80) {   // 16-row slabs, one wave per workgroup (k_rows_slab)
                     const long long items = (k1 - k0) * (N / 16);
@@ -370,43 +411,11 @@ int do_adj(ptycho_handle h, c32* f, const c32* g, const float* scan, c32* prb, i
                 HIP_TRY(hipGetLastError());
             }
         }
-        if (!split && !tiled) rc = launch_rows<N, +1>(h, ra, st);
-        if (rc) return rc;
-        ColArgs ca{};
-        ca.src = h->scratch; ca.scan = scan; ca.table = h->table; ca.ge = ge;
-        ca.order = h->order; ca.k_begin = (int)k0; ca.k_end = (int)k1; ca.strip0 = strip0; ca.nstrips = nstrips;
-        ca.det_acc = det.det_acc; ca.det = det.det;
-        if constexpr (N == 256) {
-            if (split) {
-                if (flg == 0) {
-                    ca.dst = f; ca.aux = prb;
-                    rc = launch_adjwin<N, true>(h, ca, st);
-                } else {
-                    ca.dst = prb; ca.aux = f;
-                    rc = launch_gatherwin<N, M_ADJ_PRB, true>(h, ca, st);
-                }
-                if (rc) return rc;
-                continue;
-            }
-        }
-        if (flg == 0) {
-            ca.dst = f; ca.aux = prb;
-            if (window) {
-                if constexpr (WinCfg<N>::fits) rc = launch_adjwin<N>(h, ca, st);
-            } else {
-                rc = launch_cols<N, +1, M_ADJ_OBJ>(h, ca, st);
-            }
-        } else {
-            ca.dst = prb; ca.aux = f;
-            if (h->use_window && WinCfg<N>::fits) {
-                if constexpr (WinCfg<N>::fits) rc = launch_gatherwin<N, M_ADJ_PRB>(h, ca, st);
-            } else {
-                rc = launch_cols<N, +1, M_ADJ_PRB>(h, ca, st);
-            }
-        }
+        if (rows == ROWS_PLAIN) rc = launch_rows<N, +1>(h, ra, st);
+        if (!rc) rc = launch_adj_cols<N>(h, ca, flg, st, true);
         if (rc) return rc;
     }
-    if (h->deterministic) return det_end(h, flg == 0 ? f : prb, flg, st);
+    if (h->deterministic) return det_end(h, f, prb, flg, st);
     return PTYCHO_OK;
 }
 
@@ -436,9 +445,8 @@ int do_fft2(ptycho_handle h, c32* dst, const c32* src, long long nbatch, int dir
     const long long slice = 1 << 20;
     for (long long b0 = 0; b0 < nbatch; b0 += slice) {
         const long long b1 = b0 + slice < nbatch ? b0 + slice : nbatch;
-        ColArgs ca{};
-        ca.src = dst + (size_t)b0 * N * N; ca.dst = dst + (size_t)b0 * N * N; ca.table = h->table; ca.ge = h->ge;
-        ca.order = nullptr; ca.k_begin = 0; ca.k_end = (int)(b1 - b0); ca.strip0 = 0; ca.nstrips = N / C;
+        ColArgs ca = col_args(h, nullptr, 0, b1 - b0, nullptr, C);
+        ca.src = dst + (size_t)b0 * N * N; ca.dst = dst + (size_t)b0 * N * N; ca.strip0 = 0; ca.nstrips = N / C;   // every strip
         rc = dir < 0 ? launch_cols<N, -1, M_PLAIN>(h, ca, st) : launch_cols<N, +1, M_PLAIN>(h, ca, st);
         if (rc) return rc;
     }
@@ -466,7 +474,7 @@ int launch_lines(ptycho_handle h, const c32* src, c32* dst, long long ntiles, bo
 template <int M>
 int do_fwd_generic(ptycho_handle h, c32* g, const c32* f, const float* scan, const c32* prb, hipStream_t st) {
     const Geom& ge = h->ge;
-    const long long total = (long long)ge.ptheta * ge.nscan;
+    const long long total = ge.npos();
     const long long npix = total * ge.ndet * ge.ndet;
     {
         ProfSpan ps(h, K_COLS_FWD, st);
@@ -481,7 +489,7 @@ int do_fwd_generic(ptycho_handle h, c32* g, const c32* f, const float* scan, con
 template <int M>
 int do_adj_generic(ptycho_handle h, c32* f, const c32* g, const float* scan, c32* prb, int flg, hipStream_t st) {
     const Geom& ge = h->ge;
-    const long long total = (long long)ge.ptheta * ge.nscan;
+    const long long total = ge.npos();
     const size_t tile = (size_t)ge.ndet * ge.ndet;
     // object adjoint: LDS overlap-add window over runs of sorted positions (k_adjwin_generic) when the window fits
     const size_t win_bytes = (size_t)(ge.nprb + 8) * (16 + kBucketPx) * sizeof(c32);
@@ -501,9 +509,7 @@ int do_adj_generic(ptycho_handle h, c32* f, const c32* g, const float* scan, c32
     }
     ColArgs det{};
     if (h->deterministic) {   // per-workgroup sums into the 64-bit fixed-point image (integer atomics), folded in at the end
-        if (flg == 0 && !windowed) return fail(PTYCHO_ERR_ARG, "option deterministic needs the windowed object adjoint (option window, nprb <= ~1000)");
-        int rc = det_begin(h, det, g, total * (long long)tile, flg == 0 ? prb : f,
-                           flg == 0 ? (long long)ge.ptheta * ge.nprb * ge.nprb : (long long)ge.ptheta * ge.nz * ge.n, flg, st);
+        int rc = det_begin(h, det, windowed || flg == 1, g, total * (long long)tile, f, prb, flg, st);   // the probe adjoint has no window
         if (rc) return rc;
     }
     for (long long k0 = 0; k0 < total; k0 += h->chunk) {
@@ -514,9 +520,8 @@ int do_adj_generic(ptycho_handle h, c32* f, const c32* g, const float* scan, c32
         rc = launch_lines<M, +1>(h, h->scratch, h->scratch, k1 - k0, true, nullptr, st);
         if (rc) return rc;
         if (windowed) {
-            ColArgs ca{};
-            ca.src = h->scratch; ca.dst = f; ca.aux = prb; ca.scan = scan; ca.ge = ge; ca.order = h->order;
-            ca.k_begin = (int)k0; ca.k_end = (int)k1; ca.strip0 = 0; ca.nstrips = (ge.nprb + 15) / 16;
+            ColArgs ca = col_args(h, scan, k0, k1, h->order, 16);
+            ca.src = h->scratch; ca.dst = f; ca.aux = prb; ca.strip0 = 0; ca.nstrips = (ge.nprb + 15) / 16;   // strips of the probe
             ca.det_acc = det.det_acc; ca.det = det.det;
             const int np = (int)(k1 - k0);
             const RunSplit rs = split_runs(np, ca.nstrips, h->n_cu * 4, min_seglen(np, ca.nstrips, h->n_cu));
@@ -538,7 +543,7 @@ int do_adj_generic(ptycho_handle h, c32* f, const c32* g, const float* scan, c32
         }
         HIP_TRY(hipGetLastError());
     }
-    if (h->deterministic) return det_end(h, flg == 0 ? f : prb, flg, st);
+    if (h->deterministic) return det_end(h, f, prb, flg, st);
     return PTYCHO_OK;
 }
 

@@ -5,6 +5,9 @@
 
 struct Geom {
     int ptheta, nz, n, nscan, ndet, nprb, pad;
+    __host__ __device__ long long npos() const { return (long long)ptheta * nscan; }               // scan positions
+    __host__ __device__ long long obj_elems() const { return (long long)ptheta * nz * n; }         // elements of the object
+    __host__ __device__ long long prb_elems() const { return (long long)ptheta * nprb * nprb; }    // ... of the probe
 };
 
 enum Mode { M_PLAIN = 0, M_FWD = 1, M_ADJ_OBJ = 2, M_ADJ_PRB = 3 };

@@ -26,8 +26,10 @@
 // k_rows.hpp opens with row_steps, the forward row transform that its fused CG stages, k_rows_split and the Bluestein lines of
 // k_generic.hpp share, and holds TrialTerm, the line-search term of both likelihoods;
 // frame_part.hpp before the analysis ones, which share its (frame, pixel) partition, fold and block sum), then
-// the host side by topic -- host_handle.hpp (handle, errors, profiler,
-// allocations, dispatch macros, the host's half of the partition), host_ops.hpp (launchers and the three operators), host_cg.hpp (CG stages) -- and
+// the host side by topic -- col_path.hpp (which column and row pass an operator or a CG stage runs: the rule, plain C++),
+// host_handle.hpp (handle, errors, shared argument checks, profiler, allocations, dispatch macros, the host's half of the
+// partition), host_ops.hpp (launchers, launch_fwd_cols / launch_adj_cols that switch on the rule, the three operators),
+// host_cg.hpp (CG stages and the bodies of the native stage entries, *_native) -- and
 // below them nothing but the exported functions: argument checks in the order the tests rely on, then one call.
 #include <hip/hip_runtime.h>
 
@@ -42,6 +44,7 @@
 #include "../../include/ptycho_hip.h"
 #include "fft_core.hpp"
 #include "run_split.hpp"
+#include "col_path.hpp"
 #include "adjreg_map.hpp"
 #include "k_modes.hpp"
 #include "k_frc.hpp"
@@ -222,33 +225,22 @@ long long ptycho_get(ptycho_handle h, int which) {
 }
 
 int ptycho_set_option(ptycho_handle h, const char* name, long long value) {
-    int rc = check_args(h);
-    if (rc) return rc;
+    if (int rc = check_args(h)) return rc;
     if (!name) return fail(PTYCHO_ERR_ARG, "null option name");
     if (std::strcmp(name, "chunk") == 0) {
         h->chunk = value > 0 ? value : default_chunk(h->ge);
         return free_scratch(h);
     }
-    if (std::strcmp(name, "window") == 0) {
-        h->use_window = value != 0;
-        return PTYCHO_OK;
+    static const struct { const char* name; int ptycho_handle_s::*flag; } kFlags[] = {   // on / off, nothing else to do
+        {"window", &ptycho_handle_s::use_window}, {"split", &ptycho_handle_s::use_split}, {"tile", &ptycho_handle_s::use_tile},
+        {"deterministic", &ptycho_handle_s::deterministic}, {"ls_fused_decide", &ptycho_handle_s::ls_fused_decide}};
+    for (const auto& f : kFlags) {
+        if (std::strcmp(name, f.name) == 0) { h->*f.flag = value != 0; return PTYCHO_OK; }
     }
     if (std::strcmp(name, "trust_order") == 0) {
         h->trust_order = value != 0;
         h->native_order = 0;
         if (!h->trust_order) h->order_scan = nullptr;
-        return PTYCHO_OK;
-    }
-    if (std::strcmp(name, "split") == 0) {
-        h->use_split = value != 0;
-        return PTYCHO_OK;
-    }
-    if (std::strcmp(name, "tile") == 0) {
-        h->use_tile = value != 0;
-        return PTYCHO_OK;
-    }
-    if (std::strcmp(name, "deterministic") == 0) {
-        h->deterministic = value != 0;
         return PTYCHO_OK;
     }
     if (std::strcmp(name, "model") == 0) {   // likelihood of the data stages: 0 gaussian, 1 Poisson maximum likelihood
@@ -287,16 +279,11 @@ int ptycho_set_option(ptycho_handle h, const char* name, long long value) {
         h->det_pending = false;
         return PTYCHO_OK;
     }
-    if (std::strcmp(name, "ls_fused_decide") == 0) {
-        h->ls_fused_decide = value != 0;
-        return PTYCHO_OK;
-    }
     return fail(PTYCHO_ERR_ARG, std::string("unknown option ") + name);
 }
 
 int ptycho_set_mask(ptycho_handle h, const void* mask, void* stream) {
-    int rc = check_args(h);
-    if (rc) return rc;
+    if (int rc = check_args(h)) return rc;
     if (!mask) {   // clear (the buffer stays for the next mask)
         h->mask = nullptr;
         return PTYCHO_OK;
@@ -305,15 +292,13 @@ int ptycho_set_mask(ptycho_handle h, const void* mask, void* stream) {
 }
 
 int ptycho_profile(ptycho_handle h, int enable) {
-    int rc = check_args(h);
-    if (rc) return rc;
+    if (int rc = check_args(h)) return rc;
     h->profile = enable != 0;
     return PTYCHO_OK;
 }
 
 int ptycho_profile_read(ptycho_handle h, double* ms, long long* launches, int n) {
-    int rc = check_args(h);
-    if (rc) return rc;
+    if (int rc = check_args(h)) return rc;
     if (!ms || !launches || n < 16) return fail(PTYCHO_ERR_ARG, "need arrays of at least 16 entries (18 for every kernel id)");
     for (int i = 0; i < n; ++i) { ms[i] = 0.0; launches[i] = 0; }
     for (auto& sp : h->spans) {
@@ -333,8 +318,7 @@ int ptycho_profile_read(ptycho_handle h, double* ms, long long* launches, int n)
 
 // ---- operators ----------------------------------------------------------------------------------------------------
 int ptycho_fwd(ptycho_handle h, void* g, const void* f, const void* scan, const void* prb, void* stream) {
-    int rc = check_args(h, g, f, scan, prb);
-    if (rc) return rc;
+    if (int rc = check_args(h, g, f, scan, prb)) return rc;
     hipStream_t st = (hipStream_t)stream;
     h->native_order = 0;
     if (h->bs_m) { PTY_DISPATCH_POW2(h->bs_m, (do_fwd_generic<NN>(h, (c32*)g, (const c32*)f, (const float*)scan, (const c32*)prb, st))); }
@@ -342,9 +326,8 @@ int ptycho_fwd(ptycho_handle h, void* g, const void* f, const void* scan, const 
 }
 
 int ptycho_adj(ptycho_handle h, void* f, const void* g, const void* scan, void* prb, int flg, void* stream) {
-    int rc = check_args(h, g, f, scan, prb);
-    if (rc) return rc;
-    if (flg != 0 && flg != 1) return fail(PTYCHO_ERR_ARG, "flg must be 0 (object) or 1 (probe)");
+    if (int rc = check_args(h, g, f, scan, prb)) return rc;
+    if (int rc = check_flg(flg)) return rc;
     h->native_order = 0;
     hipStream_t st = (hipStream_t)stream;
     if (h->bs_m) { PTY_DISPATCH_POW2(h->bs_m, (do_adj_generic<NN>(h, (c32*)f, (const c32*)g, (const float*)scan, (c32*)prb, flg, st))); }
@@ -352,8 +335,7 @@ int ptycho_adj(ptycho_handle h, void* f, const void* g, const void* scan, void* 
 }
 
 int ptycho_fft2(ptycho_handle h, void* dst, const void* src, size_t nbatch, int dir, void* stream) {
-    int rc = check_args(h, dst, src);
-    if (rc) return rc;
+    if (int rc = check_args(h, dst, src)) return rc;
     if (dir != -1 && dir != 1) return fail(PTYCHO_ERR_ARG, "dir must be -1 (forward) or +1 (inverse)");
     if (nbatch == 0) return PTYCHO_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -363,54 +345,47 @@ int ptycho_fft2(ptycho_handle h, void* dst, const void* src, size_t nbatch, int 
 
 // ---- CG stages, one probe -----------------------------------------------------------------------------------------
 int ptycho_cg_fwd_cols(ptycho_handle h, int slot, const void* f, const void* scan, const void* prb, void* stream) {
-    int rc = check_args(h, f, scan, prb);
-    if (rc) return rc;
+    if (int rc = check_args(h, f, scan, prb)) return rc;
     return fwd_cols_stage(h, slot, f, scan, prb, (hipStream_t)stream);
 }
 
 int ptycho_cg_adj_cols(ptycho_handle h, int slot, void* f, const void* scan, void* prb, int flg, void* stream) {
-    int rc = check_args(h, f, scan, prb);
-    if (rc) return rc;
-    if (flg != 0 && flg != 1) return fail(PTYCHO_ERR_ARG, "flg must be 0 (object) or 1 (probe)");
-    if (!slot_ready(h, slot)) return fail(PTYCHO_ERR_ARG, "work slot is empty");
+    if (int rc = check_args(h, f, scan, prb)) return rc;
+    if (int rc = check_flg(flg)) return rc;
+    if (int rc = need_slots(h, slot)) return rc;
     return adj_cols_stage(h, slot, f, scan, prb, flg, nullptr, 1, (hipStream_t)stream);
 }
 
 int ptycho_cg_stats(ptycho_handle h, int slot, const void* data, double* sums, void* stream) {
-    int rc = check_args(h, data, sums);
-    if (rc) return rc;
-    if (!slot_ready(h, slot)) return fail(PTYCHO_ERR_ARG, "work slot is empty");
+    if (int rc = check_args(h, data, sums)) return rc;
+    if (int rc = need_slots(h, slot)) return rc;
     return stats_stage(h, slot, data, sums, 0, (hipStream_t)stream);
 }
 
 int ptycho_cg_project(ptycho_handle h, int src_slot, int dst_slot, const void* data, const double* ab,
                       double* cost, void* stream) {
-    int rc = check_args(h, data, cost);
-    if (rc) return rc;
-    if (!slot_ready(h, src_slot)) return fail(PTYCHO_ERR_ARG, "work slot is empty");
+    if (int rc = check_args(h, data, cost)) return rc;
+    if (int rc = need_slots(h, src_slot)) return rc;
     return project_stage(h, src_slot, dst_slot, data, nullptr, ab, 0, cost, 0, (hipStream_t)stream);
 }
 
 int ptycho_cg_linesearch(ptycho_handle h, int slot1, int slot2, const void* data, const double* ab, double gamma0,
                          int ncand, double* costs, void* stream) {
-    int rc = check_args(h, data, costs);
-    if (rc) return rc;
-    if (ncand < 1 || ncand > kMaxCand) return fail(PTYCHO_ERR_ARG, "ncand must be in [1, 16]");
+    if (int rc = check_args(h, data, costs)) return rc;
+    if (int rc = check_ncand(ncand)) return rc;
     return linesearch_stage(h, slot1, slot2, data, LsSearch{ab, gamma0, ncand, costs, nullptr, 0}, (hipStream_t)stream);
 }
 
 // ---- CG stages, several probe modes -------------------------------------------------------------------------------
 int ptycho_cg_project_multi(ptycho_handle h, int src_slot, int dst_slot, const void* data, const void* inten,
                             const double* ab, int slot_unscaled, double* cost, void* stream) {
-    int rc = check_args(h, data, cost, inten);
-    if (rc) return rc;
-    if (!slot_ready(h, src_slot)) return fail(PTYCHO_ERR_ARG, "work slot is empty");
+    if (int rc = check_args(h, data, cost, inten)) return rc;
+    if (int rc = need_slots(h, src_slot)) return rc;
     return project_stage(h, src_slot, dst_slot, data, inten, ab, slot_unscaled ? 1 : 0, cost, 0, (hipStream_t)stream);
 }
 
 int ptycho_cg_intensity_modes(ptycho_handle h, int nmodes, void* inten, const void* data, double* sums, void* stream) {
-    int rc = check_args(h);
-    if (rc) return rc;
+    if (int rc = check_args(h)) return rc;
     if (nmodes < 1 || nmodes > kMaxModes) return fail(PTYCHO_ERR_ARG, "nmodes must be in [1, 8]");
     if (!inten && !sums) return fail(PTYCHO_ERR_ARG, "nothing to compute: inten and sums are both null");
     if (sums && !data) return fail(PTYCHO_ERR_ARG, "null operand");
@@ -419,10 +394,9 @@ int ptycho_cg_intensity_modes(ptycho_handle h, int nmodes, void* inten, const vo
 
 int ptycho_cg_linesearch_modes(ptycho_handle h, int mode0, int nmodes, const void* data, const void* inten,
                                const double* ab, double gamma0, int ncand, double* costs, void* stream) {
-    int rc = check_args(h, data, costs);
-    if (rc) return rc;
+    if (int rc = check_args(h, data, costs)) return rc;
     if (mode0 < 0 || nmodes < 1 || mode0 + nmodes > kMaxModes) return fail(PTYCHO_ERR_ARG, "modes must lie in [0, 8)");
-    if (ncand < 1 || ncand > kMaxCand) return fail(PTYCHO_ERR_ARG, "ncand must be in [1, 16]");
+    if (int rc = check_ncand(ncand)) return rc;
     if (h->compact_modes && nmodes != 1) return fail(PTYCHO_ERR_ARG, "compact slot layout: one mode pair per call (use ptycho_cg_linesearch_chunk)");
     return linesearch_modes_stage(h, mode0, nmodes, data, inten, LsSearch{ab, gamma0, ncand, costs, nullptr, 0}, (hipStream_t)stream);
 }
@@ -434,30 +408,26 @@ int ptycho_cg_fwd_cols_modes(ptycho_handle h, int nmodes, int mode0, const void*
 
 int ptycho_cg_linesearch_chunk(ptycho_handle h, int chunk, const void* data, const double* ab, double gamma0,
                                int ncand, double* costs, void* stream) {
-    int rc = check_args(h, data, costs);
-    if (rc) return rc;
+    if (int rc = check_args(h, data, costs)) return rc;
     if (!h->compact_modes || chunk < 0 || chunk >= h->sort_chunks) return fail(PTYCHO_ERR_ARG, "chunked line search needs the compact slot layout");
-    if (ncand < 1 || ncand > kMaxCand) return fail(PTYCHO_ERR_ARG, "ncand must be in [1, 16]");
+    if (int rc = check_ncand(ncand)) return rc;
     return linesearch_chunk_stage(h, chunk, data, LsSearch{ab, gamma0, ncand, costs, nullptr, 0}, (hipStream_t)stream);
 }
 
 // ---- registration (position correction) ---------------------------------------------------------------------------
 int ptycho_cg_cross(ptycho_handle h, int slot1, int slot2, double gamma, void* image_product, void* stream) {
-    int rc = check_args(h);
-    if (rc) return rc;
+    if (int rc = check_args(h)) return rc;
     return cross_public(h, slot1, slot2, gamma, nullptr, image_product, (hipStream_t)stream);
 }
 
 int ptycho_cg_cross_dev(ptycho_handle h, int slot1, int slot2, const double* gamma_dev, void* image_product, void* stream) {
-    int rc = check_args(h, gamma_dev);
-    if (rc) return rc;
+    if (int rc = check_args(h, gamma_dev)) return rc;
     return cross_public(h, slot1, slot2, 0.0, gamma_dev, image_product, (hipStream_t)stream);
 }
 
 int ptycho_cg_argmax(ptycho_handle h, int slot, void* best, void* stream) {
-    int rc = check_args(h, best);
-    if (rc) return rc;
-    if (!slot_ready(h, slot)) return fail(PTYCHO_ERR_ARG, "work slot is empty");
+    if (int rc = check_args(h, best)) return rc;
+    if (int rc = need_slots(h, slot)) return rc;
     return argmax_stage(h, slot, (unsigned long long*)best, (hipStream_t)stream);
 }
 
@@ -469,15 +439,8 @@ int ptycho_cg_zoom(ptycho_handle h, const void* image_product, const void* best,
 // ---- native CG stages: the iteration on the device-resident state -----------------------------------------------------
 int ptycho_cg_obj_begin2(ptycho_handle h, double* state, const void* psi, const void* scan, const void* prb,
                          const void* ones_prb, const void* data, void* stream) {
-    int rc = check_stage(h, state, psi, scan, prb, data);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    h->native_order = 1;   // the native loop keeps track of scan itself (ptycho_cg_obj_finish invalidates the order)
-    h->det_pending = false;
-    if (ones_prb) rc = fwd_cols_pair(h, 0, 2, psi, scan, prb, ones_prb, st);     // + slot 2 <- column pass of fwd(psi, 1)
-    else rc = fwd_cols_stage(h, 0, psi, scan, prb, st);
-    if (rc) return rc;
-    return stats_stage(h, 0, data, state + PTYCHO_ST_A, 1, st);
+    if (int rc = check_stage(h, state, psi, scan, prb, data)) return rc;
+    return obj_begin_native(h, state, psi, scan, prb, ones_prb, data, (hipStream_t)stream);
 }
 int ptycho_cg_obj_begin(ptycho_handle h, double* state, const void* psi, const void* scan, const void* prb,
                         const void* data, void* stream) {
@@ -486,16 +449,8 @@ int ptycho_cg_obj_begin(ptycho_handle h, double* state, const void* psi, const v
 
 int ptycho_cg_obj_grad(ptycho_handle h, double* state, const void* scan, void* prb, const void* data, void* grad,
                        void* stream) {
-    int rc = check_stage(h, state, scan, prb, data, grad);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const long long np = (long long)h->ge.ptheta * h->ge.nprb * h->ge.nprb;
-    // probe *= a / b (ptycho.py:344) and max |probe| (the gradient normalisation of :356 and the fixed-point scale) in one pass
-    launch_absmax(h, (const c32*)prb, np, 4, state + PTYCHO_ST_MAX_PRB, state + PTYCHO_ST_A, st);
-    h->max_prb_valid = true;
-    rc = project_stage(h, 0, 1, data, nullptr, state + PTYCHO_ST_A, 0, state + PTYCHO_ST_COST, 1, st);
-    if (rc) return rc;
-    return grad_stage(h, grad, scan, prb, 0, state + PTYCHO_ST_MAX_PRB, st);
+    if (int rc = check_stage(h, state, scan, prb, data, grad)) return rc;
+    return obj_grad_native(h, state, scan, prb, data, grad, (hipStream_t)stream);
 }
 
 int ptycho_cg_obj_dir(ptycho_handle h, double* state, int first, const void* scan, const void* prb, const void* data,
@@ -504,161 +459,67 @@ int ptycho_cg_obj_dir(ptycho_handle h, double* state, int first, const void* sca
 }
 int ptycho_cg_obj_dir2(ptycho_handle h, double* state, int first, const void* scan, const void* prb, const void* ones_prb,
                        const void* data, void* grad, void* grad0, void* dpsi, void* stream) {
-    int rc = check_stage(h, state, scan, prb, data, grad, grad0, dpsi);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const Geom& ge = h->ge;
-    const long long np = (long long)ge.ptheta * ge.nprb * ge.nprb, no = (long long)ge.ptheta * ge.nz * ge.n;
-    if (!h->max_prb_valid) launch_absmax(h, (const c32*)prb, np, 4, state + PTYCHO_ST_MAX_PRB, nullptr, st);
-    h->max_prb_valid = false;
-    dy_direction(h, state, 0, first, grad, grad0, dpsi, no, 0.0f, 0.0f, st);
-    if (ones_prb) rc = fwd_cols_pair(h, 1, 3, dpsi, scan, prb, ones_prb, st);    // + slot 3 <- column pass of fwd(dpsi, 1)
-    else rc = fwd_cols_stage(h, 1, dpsi, scan, prb, st);
-    if (rc) return rc;
-    return ls_pass(h, data, 1, state, st, 0, h->ls_fused_decide ? kLsNext[1] : -1);
+    if (int rc = check_stage(h, state, scan, prb, data, grad, grad0, dpsi)) return rc;
+    return obj_dir_native(h, state, first, scan, prb, ones_prb, data, grad, grad0, dpsi, (hipStream_t)stream);
 }
 
 int ptycho_cg_ls_next(ptycho_handle h, double* state, int which, int pass, const void* data, int use_ab, void* stream) {
-    int rc = check_stage(h, state);
-    if (rc) return rc;
+    if (int rc = check_stage(h, state)) return rc;
     if (which < 0 || which > 1 || pass < 1 || pass > 7 || !data) return fail(PTYCHO_ERR_ARG, "bad line-search stage");
-    hipStream_t st = (hipStream_t)stream;
-    if (h->ls_fused_decide) {
-        // the pass before this call has decided on its own totals and sized this one: just issue it
-        if (pass > 3) return pass == 4 ? (int)PTYCHO_OK : fail(PTYCHO_ERR_ARG, "option ls_fused_decide: passes 1, 2, 3, 4 only");
-        return ls_pass(h, data, use_ab, state, st, which, kLsNext[pass + 1]);
-    }
-    rc = ptycho_cg_ls_decide(h, state, which, kLsNext[pass], stream);
-    if (rc || pass == 4) return rc;
-    return ls_pass(h, data, use_ab, state, st, which, -1);
+    return ls_next_native(h, state, which, pass, data, use_ab, (hipStream_t)stream);
 }
 
 int ptycho_cg_obj_finish(ptycho_handle h, double* state, int correct_positions, void* psi, const void* dpsi, void* scan,
                          const void* ones_prb, const void* vt, const void* lz, int nc, int ups, double upsample_factor,
                          void* stream) {
-    int rc = check_stage(h, state, psi, dpsi, scan);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const Geom& ge = h->ge;
-    const long long no = (long long)ge.ptheta * ge.nz * ge.n;
-    if (correct_positions) {   // angle 0 only, as in the reference (ptycho.py:399-403)
-        if (!ones_prb || !vt || !lz) return fail(PTYCHO_ERR_ARG, "null operand");
-        const size_t npos = (size_t)ge.nscan;
-        if (!h->reg_ip) {
-            HIP_TRY(hipMalloc((void**)&h->reg_ip, npos * ge.ndet * ge.ndet * sizeof(c32)));
-            HIP_TRY(hipMalloc((void**)&h->reg_best, npos * sizeof(unsigned long long)));
-            HIP_TRY(hipMalloc((void**)&h->reg_shifts, npos * 2 * sizeof(double)));
-        }
-        // ptycho.py:399-402: tmp1 = fwd(psi, 1), tmp2 = fwd(psi + gamma dpsi, 1) = tmp1 + gamma fwd(dpsi, 1)
-        // 2: ptycho_cg_reg_prepare (or ptycho_cg_obj_begin2) left the column pass of tmp1 in slot 2;
-        // 3: and ptycho_cg_obj_dir2 the column pass of fwd(dpsi, 1) in slot 3
-        const int s1 = correct_positions >= 2 ? 2 : 0, s2 = correct_positions == 3 ? 3 : 1;
-        if (s1 == 0) {
-            rc = fwd_cols_stage(h, 0, psi, scan, ones_prb, st, ge.nscan);
-            if (rc) return rc;
-        }
-        if (s2 == 1) {
-            rc = fwd_cols_stage(h, 1, dpsi, scan, ones_prb, st, ge.nscan);
-            if (rc) return rc;
-        }
-        rc = cross_stage(h, s1, s2, h->reg_ip, 0.0, state + PTYCHO_ST_GAMMA_PSI, st, true);
-        if (rc) return rc;
-        rc = argmax_stage(h, s2, h->reg_best, st, true, ge.nscan);
-        if (rc) return rc;
-        // the kernel that finds the shifts also adds them to scan[0, :] (ptycho.py:403)
-        rc = zoom_impl(h, h->reg_ip, h->reg_best, vt, lz, nc, ups, upsample_factor, h->reg_shifts, (float*)scan, stream, ge.nscan);
-        if (rc) return rc;
-        h->order_scan = nullptr;   // the positions moved: the next column pass sorts again
-    }
-    hipLaunchKernelGGL(k_cg_axpy, dim3(small_grid(h, no)), dim3(256), 0, st, (c32*)psi, (const c32*)dpsi, no,
-                       (const double*)(state + PTYCHO_ST_GAMMA_PSI));
-    HIP_TRY(hipGetLastError());
-    return PTYCHO_OK;
+    if (int rc = check_stage(h, state, psi, dpsi, scan)) return rc;
+    return obj_finish_native(h, state, correct_positions, psi, dpsi, scan, ones_prb, vt, lz, nc, ups, upsample_factor, (hipStream_t)stream);
 }
 
 int ptycho_cg_reg_prepare(ptycho_handle h, double* state, const void* psi, const void* scan, const void* ones_prb, void* stream) {
-    int rc = check_stage(h, state, psi, scan, ones_prb);
-    if (rc) return rc;
+    if (int rc = check_stage(h, state, psi, scan, ones_prb)) return rc;
     return fwd_cols_stage(h, 2, psi, scan, ones_prb, (hipStream_t)stream, h->ge.nscan);
 }
 
 int ptycho_cg_prb_grad(ptycho_handle h, double* state, const void* psi, const void* scan, const void* prb,
                        const void* data, void* gprb, void* stream) {
-    int rc = check_stage(h, state, psi, scan, prb, data, gprb);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const long long no = (long long)h->ge.ptheta * h->ge.nz * h->ge.n;
-    rc = fwd_cols_stage(h, 0, psi, scan, prb, st);
-    if (rc) return rc;
-    // max |psi|: the gradient normalisation of ptycho.py:431 and the fixed-point scale of the probe adjoint
-    launch_absmax(h, (const c32*)psi, no, 4, state + PTYCHO_ST_MAX_PSI, nullptr, st);
-    h->max_psi_valid = true;
-    rc = project_stage(h, 0, 1, data, nullptr, nullptr, 0, state + PTYCHO_ST_COST2, 1, st);
-    if (rc) return rc;
-    return grad_stage(h, (void*)psi, scan, gprb, 1, state + PTYCHO_ST_MAX_PSI, st);
+    if (int rc = check_stage(h, state, psi, scan, prb, data, gprb)) return rc;
+    return prb_grad_native(h, state, psi, scan, prb, data, gprb, (hipStream_t)stream);
 }
 
 int ptycho_cg_prb_dir(ptycho_handle h, double* state, int first, double nscan_total, double nmodes, const void* psi,
                       const void* scan, const void* data, void* gprb, void* gprb0, void* dprb, void* stream) {
-    int rc = check_stage(h, state, psi, scan, data, gprb, gprb0, dprb);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const Geom& ge = h->ge;
-    const long long np = (long long)ge.ptheta * ge.nprb * ge.nprb, no = (long long)ge.ptheta * ge.nz * ge.n;
-    if (!h->max_psi_valid) launch_absmax(h, (const c32*)psi, no, 4, state + PTYCHO_ST_MAX_PSI, nullptr, st);
-    h->max_psi_valid = false;
-    dy_direction(h, state, 1, first, gprb, gprb0, dprb, np, (float)nscan_total, (float)nmodes, st);
-    rc = fwd_cols_stage(h, 1, psi, scan, dprb, st);
-    if (rc) return rc;
-    return ls_pass(h, data, 0, state, st, 1, h->ls_fused_decide ? kLsNext[1] : -1);
+    if (int rc = check_stage(h, state, psi, scan, data, gprb, gprb0, dprb)) return rc;
+    return prb_dir_native(h, state, first, nscan_total, nmodes, psi, scan, data, gprb, gprb0, dprb, (hipStream_t)stream);
 }
 
 int ptycho_cg_prb_finish(ptycho_handle h, double* state, void* prb, const void* dprb, void* stream) {
-    int rc = check_stage(h, state, prb, dprb);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const long long np = (long long)h->ge.ptheta * h->ge.nprb * h->ge.nprb;
-    hipLaunchKernelGGL(k_cg_axpy, dim3(small_grid(h, np)), dim3(256), 0, st, (c32*)prb, (const c32*)dprb, np,
-                       (const double*)(state + PTYCHO_ST_GAMMA_PRB));
-    HIP_TRY(hipGetLastError());
-    return PTYCHO_OK;
+    if (int rc = check_stage(h, state, prb, dprb)) return rc;
+    return axpy_state(h, prb, dprb, h->ge.prb_elems(), state + PTYCHO_ST_GAMMA_PRB, (hipStream_t)stream);
 }
 
 // ---- line searches of the multi-mode loop on the device-resident state (ptycho.py:383-393, 451-461 with nmodes > 1) ----
 int ptycho_cg_ls_begin(ptycho_handle h, double* state, int which, void* stream) {
-    int rc = check_stage(h, state);
-    if (rc) return rc;
-    if (which < 0 || which > 1) return fail(PTYCHO_ERR_ARG, "which must be 0 (object) or 1 (probe)");
-    hipLaunchKernelGGL(k_cg_ls_begin, dim3(1), dim3(1), 0, (hipStream_t)stream, state, which);
-    HIP_TRY(hipGetLastError());
-    return PTYCHO_OK;
+    if (int rc = check_stage(h, state)) return rc;
+    if (int rc = check_which(which)) return rc;
+    return ls_begin_native(state, which, (hipStream_t)stream);
 }
 
 int ptycho_cg_ls_decide(ptycho_handle h, double* state, int which, int next_groups, void* stream) {
-    int rc = check_stage(h, state);
-    if (rc) return rc;
+    if (int rc = check_stage(h, state)) return rc;
     if (which < 0 || which > 1 || next_groups < 0 || next_groups > kLsGroupsMax) return fail(PTYCHO_ERR_ARG, "bad line-search decision");
-    hipLaunchKernelGGL(k_cg_ls_decide, dim3(1), dim3(1), 0, (hipStream_t)stream, state, which,
-                       which == 0 ? (int)PTYCHO_ST_GAMMA_PSI : (int)PTYCHO_ST_GAMMA_PRB, next_groups);
-    HIP_TRY(hipGetLastError());
-    return PTYCHO_OK;
+    return ls_decide_native(state, which, next_groups, (hipStream_t)stream);
 }
 
 int ptycho_cg_ls_obj_chunk(ptycho_handle h, double* state, int chunk, const void* dpsi, const void* scan,
                            const void* const* prbs, const void* data, const double* ab, void* stream) {
-    int rc = check_stage(h, state, dpsi, scan, prbs, data);
-    if (rc) return rc;
+    if (int rc = check_stage(h, state, dpsi, scan, prbs, data)) return rc;
     if (!h->compact_modes || chunk < 0 || chunk >= h->sort_chunks) return fail(PTYCHO_ERR_ARG, "chunked line search needs the compact slot layout");
-    // direction column passes of this chunk, all modes side by side in the shared slot (skipped once the search is resolved)
-    rc = fwd_cols_modes_impl(h, h->compact_modes, 0, dpsi, scan, prbs, 1, chunk, stream, state + PTYCHO_ST_LS_RESOLVED);
-    if (rc) return rc;
-    // the chunks of one pass accumulate; the first one stores
-    return linesearch_chunk_stage(h, chunk, data, ls_on_state(state, ab, chunk == 0 ? 1 : 0), (hipStream_t)stream);
+    return ls_obj_chunk_native(h, state, chunk, dpsi, scan, prbs, data, ab, stream);
 }
 
 int ptycho_cg_ls_prb_pass(ptycho_handle h, double* state, int mode, const void* data, const void* inten, void* stream) {
-    int rc = check_stage(h, state, data, inten);
-    if (rc) return rc;
+    if (int rc = check_stage(h, state, data, inten)) return rc;
     if (mode < 0 || mode >= kMaxModes) return fail(PTYCHO_ERR_ARG, "modes must lie in [0, 8)");
     return linesearch_modes_stage(h, mode, 1, data, inten, ls_on_state(state, nullptr, 1), (hipStream_t)stream);
 }
@@ -678,28 +539,7 @@ int ptycho_orthogonalize_modes(void* prb, void* dprb, void* gradprb0, size_t pth
     int narr = 1;
     if (dprb) x[narr++] = (c32*)dprb;
     if (gradprb0) x[narr++] = (c32*)gradprb0;
-    const int pt = (int)ptheta;
-    const long long np = (long long)npix;
-    double* v = (double*)v_out;
-    hipStream_t st = (hipStream_t)stream;
-    switch (nmodes) {
-        case 1: return do_orthogonalize_modes<1>(x, narr, pt, np, v, powers, st);
-        case 2: return do_orthogonalize_modes<2>(x, narr, pt, np, v, powers, st);
-        case 3: return do_orthogonalize_modes<3>(x, narr, pt, np, v, powers, st);
-        case 4: return do_orthogonalize_modes<4>(x, narr, pt, np, v, powers, st);
-        case 5: return do_orthogonalize_modes<5>(x, narr, pt, np, v, powers, st);
-        case 6: return do_orthogonalize_modes<6>(x, narr, pt, np, v, powers, st);
-        case 7: return do_orthogonalize_modes<7>(x, narr, pt, np, v, powers, st);
-        case 8: return do_orthogonalize_modes<8>(x, narr, pt, np, v, powers, st);
-        case 9: return do_orthogonalize_modes<9>(x, narr, pt, np, v, powers, st);
-        case 10: return do_orthogonalize_modes<10>(x, narr, pt, np, v, powers, st);
-        case 11: return do_orthogonalize_modes<11>(x, narr, pt, np, v, powers, st);
-        case 12: return do_orthogonalize_modes<12>(x, narr, pt, np, v, powers, st);
-        case 13: return do_orthogonalize_modes<13>(x, narr, pt, np, v, powers, st);
-        case 14: return do_orthogonalize_modes<14>(x, narr, pt, np, v, powers, st);
-        case 15: return do_orthogonalize_modes<15>(x, narr, pt, np, v, powers, st);
-        default: return do_orthogonalize_modes<16>(x, narr, pt, np, v, powers, st);
-    }
+    return orthogonalize_modes(nmodes, x, narr, (int)ptheta, (long long)npix, (double*)v_out, powers, (hipStream_t)stream);
 }
 
 // ---- Fourier ring correlation (k_frc.hpp, libtike.hipfft.frc) ------------------------------------------------------------
@@ -756,7 +596,7 @@ int ptycho_gauge_fit(double* gauge, const void* psi, const void* ref, const floa
 int ptycho_gauge_apply(void* x, const double* gauge, size_t ptheta, size_t ny, size_t nx, int which, void* stream) {
     if (!x || !gauge) return fail(PTYCHO_ERR_ARG, "x and gauge must not be null");
     if (ptheta == 0 || ny == 0 || nx == 0) return fail(PTYCHO_ERR_ARG, "all sizes must be positive");
-    if (which != 0 && which != 1) return fail(PTYCHO_ERR_ARG, "which must be 0 (object) or 1 (probe)");
+    if (int rc = check_which(which)) return rc;
     if (ptheta > kGaugeMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
     if (ny > kGaugeMaxSide || nx > kGaugeMaxSide || ((nx + 255) / 256) * ny > 0x7fffffffull)
         return fail(PTYCHO_ERR_ARG, "ny or nx too large for one launch");
@@ -877,8 +717,7 @@ size_t ptycho_propagate_work_words(ptycho_handle h, size_t nfield, size_t nplane
 
 int ptycho_propagate(ptycho_handle h, void* planes, double* metrics, const void* spec, size_t nfield, const double* zl,
                      size_t nplane, double q0, int method, void* work, void* stream) {
-    int rc = check_args(h);
-    if (rc) return rc;
+    if (int rc = check_args(h)) return rc;
     if (!spec || !zl || !work) return fail(PTYCHO_ERR_ARG, "spec, zl and work must not be null");
     if (!planes && !metrics) return fail(PTYCHO_ERR_ARG, "nothing to compute: planes and metrics are both null");
     if (!frc_size_ok(h->ge.ndet)) return fail(PTYCHO_ERR_ARG, "the handle's ndet must be in [16, 1024] or 2048");

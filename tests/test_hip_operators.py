@@ -422,3 +422,51 @@ def test_deterministic_adjoints_are_bitwise_reproducible(pt, ndet, nprb):
         np.testing.assert_array_equal(b, runs[0][1])
     assert np.abs(runs[0][0] - ref_a).max() <= 2e-6 * np.abs(ref_a).max()
     assert np.abs(runs[0][1] - ref_b).max() <= 2e-6 * np.abs(ref_b).max()
+
+
+# Launches per kernel id of one fwd / adj / adj_probe call each (in-library profiler), by detector size and options: the
+# record of which path the host dispatch takes.  None: the call is not part of the row.  One angle, 4 x 5 positions,
+# nprb = ndet, a scan tensor of its own per call, all three alive (so every call that sorts the positions does sort them).
+SORT, TILE_F, TILE_P = "sort_positions", "k_fwd_tile", "k_adjprb_tile"
+CF, CO, CP, RF, RI = "k_cols<FWD>", "k_cols<ADJ_OBJ>", "k_cols<ADJ_PRB>", "k_rows<fwd>", "k_rows<inv>"
+LEDGER = [
+    # ndet, options, fwd, adj, adj_probe
+    (64, {}, {TILE_F: 1}, {SORT: 1, RI: 1, CO: 1}, {TILE_P: 1}),
+    (64, {"tile": 0}, {SORT: 1, CF: 1, RF: 1}, {SORT: 1, RI: 1, CO: 1}, {SORT: 1, RI: 1, CP: 1}),
+    (64, {"tile": 0, "window": 0}, {CF: 1, RF: 1}, {SORT: 1, RI: 1, CO: 1}, None),
+    (256, {}, None, {SORT: 1, RI: 1, CO: 1}, None),
+    (256, {"chunk": 7}, None, {SORT: 1, RI: 3, CO: 3}, None),
+    (100, {}, {CF: 1, RF: 2}, {SORT: 1, RI: 2, CO: 1}, {RI: 2, CP: 1}),   # Bluestein lines: a row and a column launch
+]
+
+
+def test_launch_ledger_of_the_operators(pt):
+    import torch
+    bad = []
+    for ndet, options, want_fwd, want_adj, want_prb in LEDGER:
+        p = syn.make_problem(4, 5, 5, ndet, ndet, seed=3)
+        assert p["nscan"] == 20 and p["nz"] < ndet + 100 and p["n"] < ndet + 100
+        with pt.PtychoCuFFT(20, ndet, ndet, 1, p["nz"], p["n"]) as slv:
+            if "tile" in options:
+                slv.set_tile(options["tile"])
+            if "window" in options:
+                slv.set_window(options["window"])
+            if "chunk" in options:
+                slv.set_chunk(options["chunk"])
+            psi, prb = dev(p["psi"]), dev(p["probe"])
+            scans = [dev(p["scan"]) for _ in range(3)]
+            y = torch.ones((1, 20, ndet, ndet), dtype=torch.complex64, device="cuda")
+            assert y.data_ptr() % 16 == 0
+            slv.profile(True)
+            for name, want, call in (("fwd", want_fwd, lambda: slv.fwd(psi, scans[0], prb)),
+                                     ("adj", want_adj, lambda: slv.adj(y, scans[1], prb)),
+                                     ("adj_probe", want_prb, lambda: slv.adj_probe(y, scans[2], psi))):
+                if want is None:
+                    continue
+                call()
+                got = {k: n for k, (_, n) in slv.profile_read().items()}
+                print("ledger", ndet, options, name, got)
+                if got != want:
+                    bad.append((ndet, options, name, got, want))
+            slv.profile(False)
+    assert not bad, bad
