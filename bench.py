@@ -11,13 +11,19 @@ update, which is the path's one real exchange step.  Scan positions are sharded
 over ranks (weak scaling: 4096 positions per GPU on a common object).
 
 Rank 0 prints ONE JSON line.  ``value`` is whole-job fwd+adj patterns/s with all
-inputs resident in HBM.  ``roofline`` prices the fwd+adj pair against the HBM
-roofline with the algorithmic bytes of BASELINE.md section 3 and reports live
-per-kernel durations (HIP events on the launch stream, taken inside the library);
-``cpu_baseline`` times the NumPy/SciPy oracle on a bounded sample on this host's
-cores.  Secondary: ``cg_iterations_per_s`` (the reference CG loop on the same
-problem, 50 iterations) and, for N > 1, ``cg_strong_iterations_per_s`` (the same 4096
-positions split over the ranks: strong scaling of the CG loop).
+inputs resident in HBM, and ``roofline`` prices ``ms_per_step`` against the HBM
+roofline with the algorithmic bytes of BASELINE.md section 3.  A plain run does
+nothing else: set-up, warm-up, the timed steps, ``--dump-outputs``, the line.
+
+``--full`` adds every other figure to the same line, each from runs of its own
+after the timed steps: the pair with the position order recomputed in every call,
+live per-kernel durations in ``roofline`` (HIP events on the launch stream, taken
+inside the library), ``cpu_baseline`` (the NumPy/SciPy oracle on a bounded sample
+on this host's cores), ``cg_iterations_per_s`` (the reference CG loop on the same
+problem, 50 iterations), for N > 1 ``cg_strong_iterations_per_s`` (the same 4096
+positions split over the ranks: strong scaling of the CG loop), and on one GPU the
+other configurations of BASELINE.json and the other detector sizes.  ``--no-cpu``,
+``--no-cg``, ``--no-cfg3`` and ``--no-shard`` leave parts of that out.
 
 ``--dump-outputs DIR`` writes what the last timed step returned (``dump_outputs``): the
 inputs are seeded, so two builds can be compared output for output.
@@ -48,6 +54,10 @@ def parse():
     ap.add_argument("--nprb", type=int, default=256)
     ap.add_argument("--raster", type=int, default=64, help="raster is RxR positions per GPU")
     ap.add_argument("--step-px", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure every secondary figure (sorting in every call, per-kernel "
+                         "durations, CG iterations/s, the CPU baseline, the other configurations and detector sizes); "
+                         "--cg-iters, --cpu-sample, --cfg3-iters and the --no-* options below apply to these only")
     ap.add_argument("--cg-iters", type=int, default=50)   # BASELINE.json configs[1]: 50 CG iterations
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--cpu-sample", type=int, default=192)
@@ -406,7 +416,6 @@ def main():
     ngpu = world
 
     import libtike.hipfft as pt
-    from libtike.hipfft import synthetic as syn
 
     R, step, nprb, ndet = args.raster, args.step_px, args.nprb, args.ndet
     nscan = R * R
@@ -482,7 +491,57 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = ngpu * nscan * args.steps / elapsed
     if args.dump_outputs and rank == 0:
-        dump_outputs(args.dump_outputs, g_buf, upd)     # before the loops below overwrite both buffers
+        dump_outputs(args.dump_outputs, g_buf, upd)     # before the loops of --full overwrite both buffers
+
+    op_bytes = 8.0 * nscan * ndet * ndet + 8.0 * nz * n + 8.0 * nprb * nprb + 8.0 * nscan
+    pair_bytes = 2.0 * op_bytes                       # BASELINE.md section 3
+    achieved = pair_bytes / (1e-3 * ms_per_step) / 1e9
+    out = {
+        "metric": "fwd+adj patterns/s",
+        "value": value, "unit": "patterns/s",
+        "n_gpus": ngpu, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "timed_region_note": "value / ms_per_step: the position order is computed once (scan unchanged between calls)",
+        "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "%d scan positions/GPU x (%dx%d) detector, complex64, nprb=%d, "
+                               "1 probe mode, object %dx%d, raster step %d px + jitter "
+                               "(BASELINE.json configs[1])" % (nscan, ndet, ndet, nprb, nz, n, step),
+                   "nscan_per_gpu": nscan, "ndet": ndet, "nprb": nprb, "object": [nz, n],
+                   "sharding": "scan positions over ranks, object all-reduce (RCCL)" if ngpu > 1 else "single GPU",
+                   "chunk": int(args.chunk)},
+        "roofline": {
+            "bound": "hbm",
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            "what": "fwd+adj pair: %.4e algorithmic B per %d-position batch (16*ndet^2 B/pattern "
+                    "+ object, probe, scan) / measured ms_per_step" % (pair_bytes, nscan),
+        },
+        "full": bool(args.full),
+    }
+    if args.full:
+        pair_figures(out, args, slv, psi, scan, prb, prob, g_buf, upd_buf, fence, dist, rank)
+    slv.free()
+    if args.full and ngpu == 1 and not dist and not args.no_cg:
+        del psi, scan, prb, g_buf, upd_buf, upd_bufs, upd
+        torch.cuda.empty_cache()
+        other_config_figures(out, args, dev)
+    if dist:
+        dist.barrier()
+        dist.destroy_process_group()
+    sys.stdout.flush()
+    os.dup2(real_stdout, 1)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+
+
+def pair_figures(out, args, slv, psi, scan, prb, prob, g_buf, upd_buf, fence, dist, rank):
+    """--full, on the solver and inputs of the timed steps: adds to the result line ``out`` the pair with the position
+    order recomputed in every call, the live per-kernel durations (into ``roofline``), the CG loop and the CPU baseline."""
+    import libtike.hipfft as pt
+    from libtike.hipfft import synthetic as syn
+    dev, prb_h, nz, n = psi.device, prob["probe"], prob["nz"], prob["n"]
+    R, step, nprb, ndet = args.raster, args.step_px, args.nprb, args.ndet
+    nscan, ngpu = R * R, out["n_gpus"]
 
     # The timed steps reuse the position order of the first call (the scan tensor is unchanged: option trust_order).
     # A caller whose positions change between calls pays the sort in both operators: same step, order forgotten
@@ -519,8 +578,6 @@ def main():
     kernel_ms = sum(v["ms_per_step"] for v in kern.values())
     dominant = max(kern, key=lambda k: kern[k]["ms_per_step"])
     op_bytes = 8.0 * nscan * ndet * ndet + 8.0 * nz * n + 8.0 * nprb * nprb + 8.0 * nscan
-    pair_bytes = 2.0 * op_bytes                       # BASELINE.md section 3
-    achieved = pair_bytes / (1e-3 * ms_per_step) / 1e9
     # the dominant kernel against its own operator's compulsory bytes per launch
     dom = kern[dominant]
     dom_bytes = op_bytes / dom["launches_per_step"]
@@ -538,12 +595,8 @@ def main():
             traffic_src = tj["source"]
     except Exception:
         pass
-    roofline = {
-        "bound": "hbm",
-        "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+    out["roofline"].update({
         "traffic": traffic, "traffic_unit": "HBM bytes per step (fwd+adj pair), PMC", "traffic_source": traffic_src,
-        "what": "fwd+adj pair: %.4e algorithmic B per %d-position batch (16*ndet^2 B/pattern "
-                "+ object, probe, scan) / measured ms_per_step" % (pair_bytes, nscan),
         # the kernel with the longest duration per step.  Two different questions, two keys: (1) what share of the operator's
         # ALGORITHMIC bytes its duration alone would allow ("operator_bytes_over_this_kernel": a ceiling on the operator's own
         # fraction, NOT a kernel efficiency -- the operator has a second kernel); (2) how fast the kernel moves the bytes it
@@ -561,13 +614,12 @@ def main():
         },
         "kernels": kern,
         "kernel_ms_per_step": kernel_ms, "pair_ms_hip_events": pair_ms_events,
-    }
+    })
 
     # ---- CG iterations / s (secondary metric of BASELINE.json) -------------------
     cg = None
     if not args.no_cg and args.cg_iters > 0:
         data = (torch.abs(slv.fwd(psi, scan, prb, out=g_buf)) ** 2).contiguous()
-        g_buf = None
         psi0 = torch.ones_like(psi)
         slv.run(data, psi0, scan.clone(), prb[:, None].clone(), piter=2)     # warm-up
         fence()
@@ -617,10 +669,7 @@ def main():
             # this geometry against the oracle at 8 x 8 positions
             rs = np.random.default_rng(4242)
             prb_s = torch.as_tensor((prb_h * np.exp(2j * np.pi * rs.random(prb_h.shape[-2:]))).astype(np.complex64), device=dev)
-            if data is None or g_buf is None:
-                g_buf = torch.empty((1, nscan, ndet, ndet), dtype=torch.complex64, device=dev)
             data_s = (torch.abs(slv.fwd(psi, scan, prb_s, out=g_buf)) ** 2).contiguous()
-            g_buf = None
             slv.run(data_s, psi0, scan.clone(), prb_s[:, None].clone(), piter=2)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -641,57 +690,38 @@ def main():
             cg.update(screened)
         del data
 
-    out = {
-        "metric": "fwd+adj patterns/s",
-        "value": value, "unit": "patterns/s",
-        "n_gpus": ngpu, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "ms_per_step_sorting_every_call": ms_per_step_sorting,
-        "timed_region_note": "value / ms_per_step: the position order is computed once (scan unchanged between calls); "
-                             "ms_per_step_sorting_every_call: the same pair with the order recomputed in fwd and in adj"
-                             + (" (no all-reduce in this second loop)" if ngpu > 1 else ""),
-        "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "%d scan positions/GPU x (%dx%d) detector, complex64, nprb=%d, "
-                               "1 probe mode, object %dx%d, raster step %d px + jitter "
-                               "(BASELINE.json configs[1])" % (nscan, ndet, ndet, nprb, nz, n, step),
-                   "nscan_per_gpu": nscan, "ndet": ndet, "nprb": nprb, "object": [nz, n],
-                   "sharding": "scan positions over ranks, object all-reduce (RCCL)" if ngpu > 1 else "single GPU",
-                   "chunk": int(args.chunk)},
-        "roofline": roofline,
-    }
+    out["ms_per_step_sorting_every_call"] = ms_per_step_sorting
+    out["timed_region_note"] += ("; ms_per_step_sorting_every_call: the same pair with the order recomputed in fwd and in adj"
+                                 + (" (no all-reduce in this second loop)" if ngpu > 1 else ""))
     if cg:
         out.update(cg)
     if rank == 0 and ngpu == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(args, prob)
     elif rank == 0:
         out["cpu_baseline"] = None
-    slv.free()
-    if ngpu == 1 and not dist and not args.no_cg:
-        del psi, scan, prb
-        torch.cuda.empty_cache()
-        if not args.no_cfg3:
-            try:
-                out.update(cfg3_figures(pt, syn, dev, args.cfg3_iters))
-            except Exception as e:          # never let a secondary figure break the primary line
-                print("configs[2] figures failed: %r" % (e,), file=sys.stderr)
+
+
+def other_config_figures(out, args, dev):
+    """--full on one GPU, after the solver of the timed steps is freed: adds to the result line ``out`` the figures of the
+    other configurations of BASELINE.json and of the other detector sizes.  None of them may break the primary line."""
+    import libtike.hipfft as pt
+    from libtike.hipfft import synthetic as syn
+    if not args.no_cfg3:
         try:
-            out.update(generic_figures(pt, syn, dev))
-            out.update(small_tile_figures(pt, syn, dev))
+            out.update(cfg3_figures(pt, syn, dev, args.cfg3_iters))
         except Exception as e:
-            print("generic-size figures failed: %r" % (e,), file=sys.stderr)
-        if not args.no_shard:
-            try:
-                torch.cuda.empty_cache()
-                out.update(shard_and_stream_figures(pt, syn, dev))
-            except Exception as e:
-                print("configs[3] shard / configs[4] streaming figures failed: %r" % (e,), file=sys.stderr)
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
-    sys.stdout.flush()
-    os.dup2(real_stdout, 1)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
+            print("configs[2] figures failed: %r" % (e,), file=sys.stderr)
+    try:
+        out.update(generic_figures(pt, syn, dev))
+        out.update(small_tile_figures(pt, syn, dev))
+    except Exception as e:
+        print("generic-size figures failed: %r" % (e,), file=sys.stderr)
+    if not args.no_shard:
+        try:
+            torch.cuda.empty_cache()
+            out.update(shard_and_stream_figures(pt, syn, dev))
+        except Exception as e:
+            print("configs[3] shard / configs[4] streaming figures failed: %r" % (e,), file=sys.stderr)
 
 
 if __name__ == "__main__":

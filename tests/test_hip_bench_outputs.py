@@ -17,7 +17,7 @@ R, STEP, NDET = 16, 8, 256
 
 def run_bench(out):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--no-cpu", "--no-cg", "--raster", str(R), "--step-px", str(STEP), "--dump-outputs", str(out)]
+           "--raster", str(R), "--step-px", str(STEP), "--dump-outputs", str(out)]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -38,6 +38,11 @@ def test_dumped_outputs_are_reproducible_and_right(tmp_path):
     d = run_bench(tmp_path / "a")
     run_bench(tmp_path / "b")
     assert d["steps"] == 3 and d["ms_per_step"] > 0
+    # a plain run (no --full): the headline figure and nothing that takes runs of its own
+    assert d["metric"] == "fwd+adj patterns/s" and d["unit"] == "patterns/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["value"] == pytest.approx(R * R / (d["ms_per_step"] * 1e-3))
+    assert d["full"] is False and "kernels" not in d["roofline"]
+    assert not [k for k in d if k.startswith(("cg_", "cfg", "cpu_", "ndet", "generic", "bluestein", "ms_per_step_sorting"))]
     names = sorted(os.listdir(tmp_path / "a"))
     assert names == ["farplane.npy", "object.npy"]
     assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64e6

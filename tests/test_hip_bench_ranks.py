@@ -1,5 +1,5 @@
 """``bench.py`` with more than one rank (the driver's N = 2, 4, 8 runs): two ``gloo`` ranks share the test box's one
-GPU (``BENCH_SINGLE_DEVICE=1``; RCCL refuses two ranks on one device) and run the whole script on a small raster --
+GPU (``BENCH_SINGLE_DEVICE=1``; RCCL refuses two ranks on one device) and run the whole script (``--full``) on a small raster --
 weak-scaling step with its object all-reduce, CG leg, strong-scaling CG leg.  Every collective must be issued the
 same number of times on both ranks: a wall-clock-bounded loop around one (as the clock-ramp loop of round 2 once
 was) hangs here, and the time limit turns that into a failure."""
@@ -22,7 +22,8 @@ def test_bench_runs_with_two_ranks():
     port = 29800 + (os.getpid() % 1000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-cfg3", "--cg-iters", "3", "--raster", "16"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-cfg3", "--cg-iters", "3",
+           "--raster", "16"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -44,7 +45,7 @@ def test_bench_runs_on_rccl_with_one_rank():
     env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--no-cpu", "--no-cfg3", "--cg-iters", "3", "--raster", "16"]
+           "--full", "--no-cpu", "--no-cfg3", "--cg-iters", "3", "--raster", "16"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
