@@ -309,6 +309,55 @@ size_t ptycho_propagate_work_words(ptycho_handle h, size_t nfield, size_t nplane
 int ptycho_propagate(ptycho_handle h, void* planes, double* metrics, const void* spec, size_t nfield, const double* zl,
                      size_t nplane, double q0, int method, void* work, void* stream);
 
+/* B-spline resampling of images (no handle; libtike.hipfft.resample): the prefilter, the affine warp and the moments
+ * behind a centre of mass.  Everything runs on `stream`, nothing synchronises, no atomics and fixed summation orders: the
+ * same inputs give the same bits.  An image is [ny][nx] of float32 (cplx = 0) or complex64 (cplx != 0, real and imaginary
+ * part treated alike); nimg in [1, 65535], 2 <= ny, nx <= 65536, ny * nx < 2^31.  Interpolation is by B-splines of order
+ * 0 ... 5 as scipy.ndimage does it, with MIRROR extension: whole-sample symmetric, period 2 n - 2, refl(i) the index in
+ * [0, n) that i reflects to.
+ *   ptycho_spline_prefilter   out <- the B-spline coefficients of in along both axes (orders 0 and 1: a copy).  Per axis
+ *       and pole z (order 2: sqrt 8 - 3; 3: sqrt 3 - 2; 4: -0.36134, -0.013725; 5: -0.43058, -0.043096, closed forms in
+ *       float64, rounded to float32), after multiplication by the gain prod (1 - z)(1 - 1 / z):
+ *       c+[0] = sum over the mirrored line of z^|k| x[k], c+[k] = x[k] + z c+[k-1],
+ *       c[n-1] = (z c+[n-2] + c+[n-1]) z / (z^2 - 1), c[k] = z (c[k+1] - c+[k]); two poles cascade.  This is
+ *       scipy.ndimage.spline_filter(mode="mirror").  A line is cut into segments of PTYCHO_SPLINE_SEGMENT samples; a
+ *       segment is filtered over itself and a halo of 12 / 16 / 28 / 32 samples (orders 2 ... 5) on either side, exactly
+ *       where that range touches an end of the line and from zero state elsewhere, which is off by at most 1e-9 of the
+ *       line's largest value.  Arithmetic is float32.  Columns first (in -> work), then rows (work -> out): out may be
+ *       in.  work: ptycho_spline_work_words float64 words (0 for sizes out of range), neither out nor in.  16-byte
+ *       accesses when nx * (cplx ? 2 : 1) is a multiple of 4 and out, in and work are 16-byte aligned.  Two launches.
+ *   ptycho_warp   out[i] (oh x ow) <- coef[i] (ny x nx, coefficients of ptycho_spline_prefilter) under the affine map
+ *       xf[i] = (m00, m01, m10, m11, offy, offx), float64 ON THE DEVICE: output pixel (oy, ox) has the source coordinate
+ *       sy = (m00 oy + m01 ox) + offy, sx = (m10 oy + m11 ox) + offx in float64, every operation rounded on its own
+ *       (the geometry of scipy.ndimage.affine_transform).  Per axis the first tap is b = floor(s) - order / 2 for odd and
+ *       floor(s + 1/2) - order / 2 for even orders, t = s - floor(.) in float32, and the value is
+ *       sum_a wy[a] (sum_b wx[b] coef[refl(by + a)][refl(bx + b)]) in float32, w the centred cardinal B-spline at
+ *       t + order / 2 - a.  flags: PTYCHO_WARP_MIRROR evaluates every pixel (a coordinate beyond 2^30 in magnitude or
+ *       not finite still gives cval); without it a coordinate within 2^-20 of the extent [0, ny-1] x [0, nx-1] is clamped
+ *       onto it and a pixel outside gets (cval_re, cval_im).  A 32 x 32 output tile stages the box of coefficients that its
+ *       taps touch in LDS when the box holds at most 4096 elements and reads global memory otherwise (strong
+ *       minification); PTYCHO_WARP_GLOBAL forces the latter; both give the same bits.  path: NULL, or int32
+ *       [nimg][ceil(oh / 32)][ceil(ow / 32)] that receives per tile 0 (wholly outside: cval, nothing loaded), 1 (LDS) or
+ *       2 (global).  out must not be coef.  One launch.
+ *   ptycho_moments   sums (float64 [nimg][5]) <- sum w, sum w y, sum w x, sum w y^2, sum w x^2 over the pixels (y, x) of
+ *       each image, in float64.  w is float32: which = 0 the value, 1 its positive part, 2 its square, for a complex
+ *       image (which = 2 only) round(round(re re) + round(im im)); times weight (float32 [nimg][ny][nx]) if not NULL,
+ *       rounded once.  work: ptycho_moments_work_words float64 words (0 for sizes out of range).  Two launches.
+ * PTYCHO_ERR_ARG, before any HIP call, for a null out / in / work / coef / xf / sums / x, nimg outside [1, 65535], a side
+ * below 2 or above 65536, ny * nx >= 2^31, an output side of 0 or above 65536, oh * ow >= 2^31, an order outside
+ * [0, 5], unknown flags, work equal to out or in, out equal to coef, which outside [0, 2], a complex image with which != 2. */
+#define PTYCHO_SPLINE_SEGMENT 64
+#define PTYCHO_WARP_MIRROR 1
+#define PTYCHO_WARP_GLOBAL 2
+size_t ptycho_spline_work_words(size_t nimg, size_t ny, size_t nx, int cplx);
+int ptycho_spline_prefilter(void* out, const void* in, size_t nimg, size_t ny, size_t nx, int cplx, int order, void* work,
+                            void* stream);
+int ptycho_warp(void* out, const void* coef, const double* xf, size_t nimg, size_t ny, size_t nx, size_t oh, size_t ow,
+                int cplx, int order, int flags, float cval_re, float cval_im, int* path, void* stream);
+size_t ptycho_moments_work_words(size_t nimg, size_t ny, size_t nx);
+int ptycho_moments(double* sums, const void* x, const float* weight, size_t nimg, size_t ny, size_t nx, int cplx, int which,
+                   double* work, void* stream);
+
 /* ---- fused CG-stage entry points ("plus fused CG-stage entry points") ----
  * The elementwise stages of CGPtychoSolver.run (src/libtike/cufft/ptycho.py:325-393) are
  * fused into the row pass of the DFT so that farplanes are never materialised.  The

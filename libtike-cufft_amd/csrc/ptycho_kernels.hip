@@ -52,6 +52,7 @@
 #include "k_fit.hpp"
 #include "k_prepare.hpp"
 #include "k_unwrap.hpp"
+#include "k_resample.hpp"
 
 using namespace pty;
 
@@ -78,6 +79,7 @@ namespace {
 #include "host_prepare.hpp"
 #include "host_unwrap.hpp"
 #include "host_propagate.hpp"
+#include "host_resample.hpp"
 
 extern "C" {
 
@@ -730,6 +732,80 @@ int ptycho_propagate(ptycho_handle h, void* planes, double* metrics, const void*
     hipStream_t st = (hipStream_t)stream;
     if (h->bs_m) { PTY_DISPATCH_POW2(h->bs_m, (do_propagate_generic<NN>(h, a, st))); }
     PTY_DISPATCH(h->ge.ndet, (do_propagate<NN>(h, a, st)));
+}
+
+// ---- B-spline resampling: prefilter, affine warp, moments (k_resample.hpp, libtike.hipfft.resample): no handle ------------
+static int resample_check_sizes(size_t nimg, size_t ny, size_t nx, const char* what) {
+    if (nimg == 0 || nimg > kRsMaxImages) return fail(PTYCHO_ERR_ARG, "nimg must be in [1, 65535]");
+    if (ny < 2 || nx < 2) return fail(PTYCHO_ERR_ARG, std::string(what) + " sides must be at least 2");
+    if (!resample_sizes_ok(nimg, ny, nx))
+        return fail(PTYCHO_ERR_ARG, std::string(what) + " sides must be at most 65536 and their product below 2^31");
+    return PTYCHO_OK;
+}
+
+size_t ptycho_spline_work_words(size_t nimg, size_t ny, size_t nx, int cplx) {
+    if (!resample_sizes_ok(nimg, ny, nx)) return 0;
+    return (nimg * ny * nx * (cplx ? 2 : 1) + 1) / 2;
+}
+
+int ptycho_spline_prefilter(void* out, const void* in, size_t nimg, size_t ny, size_t nx, int cplx, int order, void* work,
+                            void* stream) {
+    if (!out || !in || !work) return fail(PTYCHO_ERR_ARG, "out, in and work must not be null");
+    if (int rc = resample_check_sizes(nimg, ny, nx, "image")) return rc;
+    if (order < 0 || order > 5) return fail(PTYCHO_ERR_ARG, "order must be in [0, 5]");
+    if (work == out || work == in) return fail(PTYCHO_ERR_ARG, "work must be neither out nor in");
+    hipStream_t st = (hipStream_t)stream;
+    const int C = cplx ? 2 : 1;
+    float* o = (float*)out;
+    const float* i = (const float*)in;
+    switch (order) {
+        case 2: return do_spline_prefilter<2>(o, i, (int)nimg, (int)ny, (int)nx, C, (float*)work, st);
+        case 3: return do_spline_prefilter<3>(o, i, (int)nimg, (int)ny, (int)nx, C, (float*)work, st);
+        case 4: return do_spline_prefilter<4>(o, i, (int)nimg, (int)ny, (int)nx, C, (float*)work, st);
+        case 5: return do_spline_prefilter<5>(o, i, (int)nimg, (int)ny, (int)nx, C, (float*)work, st);
+        default: break;   // orders 0 and 1 interpolate the samples themselves
+    }
+    if (out != in) HIP_TRY(hipMemcpyAsync(out, in, nimg * ny * nx * C * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return PTYCHO_OK;
+}
+
+int ptycho_warp(void* out, const void* coef, const double* xf, size_t nimg, size_t ny, size_t nx, size_t oh, size_t ow,
+                int cplx, int order, int flags, float cval_re, float cval_im, int* path, void* stream) {
+    if (!out || !coef || !xf) return fail(PTYCHO_ERR_ARG, "out, coef and xf must not be null");
+    if (int rc = resample_check_sizes(nimg, ny, nx, "image")) return rc;
+    if (oh == 0 || ow == 0) return fail(PTYCHO_ERR_ARG, "output sides must be positive");
+    if (oh > kRsMaxSide || ow > kRsMaxSide || oh * ow >= kRsMaxPixels)
+        return fail(PTYCHO_ERR_ARG, "output sides must be at most 65536 and their product below 2^31");
+    if (order < 0 || order > 5) return fail(PTYCHO_ERR_ARG, "order must be in [0, 5]");
+    if (flags & ~(RS_MIRROR | RS_GLOBAL)) return fail(PTYCHO_ERR_ARG, "flags must be a combination of 1 (mirror) and 2 (global)");
+    if (out == coef) return fail(PTYCHO_ERR_ARG, "out must not be coef");
+    hipStream_t st = (hipStream_t)stream;
+#define WARP_CASE(O)                                                                                                      \
+    case O: return do_warp<O>(out, coef, xf, (int)nimg, (int)ny, (int)nx, (int)oh, (int)ow, cplx, flags, cval_re, cval_im, path, st)
+    switch (order) {
+        WARP_CASE(0);
+        WARP_CASE(1);
+        WARP_CASE(2);
+        WARP_CASE(3);
+        WARP_CASE(4);
+        default: break;
+    }
+    return do_warp<5>(out, coef, xf, (int)nimg, (int)ny, (int)nx, (int)oh, (int)ow, cplx, flags, cval_re, cval_im, path, st);
+#undef WARP_CASE
+}
+
+size_t ptycho_moments_work_words(size_t nimg, size_t ny, size_t nx) {
+    if (!resample_sizes_ok(nimg, ny, nx)) return 0;
+    return nimg * (size_t)rs_moment_blocks((long long)(ny * nx)) * kRsMomWords;
+}
+
+int ptycho_moments(double* sums, const void* x, const float* weight, size_t nimg, size_t ny, size_t nx, int cplx, int which,
+                   double* work, void* stream) {
+    if (!sums || !x || !work) return fail(PTYCHO_ERR_ARG, "sums, x and work must not be null");
+    if (int rc = resample_check_sizes(nimg, ny, nx, "image")) return rc;
+    if (which < 0 || which > 2) return fail(PTYCHO_ERR_ARG, "which must be 0 (value), 1 (positive) or 2 (power)");
+    if (cplx && which != RS_POWER) return fail(PTYCHO_ERR_ARG, "a complex image has no value or positive part: which must be 2");
+    return do_moments(sums, (const float*)x, weight, (int)nimg, (int)ny, (int)nx, cplx != 0, which, work, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -7,5 +7,6 @@ from libtike.hipfft.fit import fit_frames, accumulate_intensity, flag_frames  # 
 from libtike.hipfft.prepare import prepare_frames, initial_probe  # noqa: F401
 from libtike.hipfft.unwrap import unwrap_phase, phase_residues  # noqa: F401
 from libtike.hipfft.propagate import propagate, focus_series, object_pixel_size  # noqa: F401
+from libtike.hipfft.resample import spline_prefilter, warp, rotate, zoom, shift, center_of_mass  # noqa: F401
 
 __version__ = "0.1.0"

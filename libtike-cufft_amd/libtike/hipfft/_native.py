@@ -34,6 +34,8 @@ SYMBOLS = ("ptycho_create", "ptycho_free", "ptycho_destroy", "ptycho_get",
            "ptycho_unwrap_work_words", "ptycho_unwrap_buffer_floats", "ptycho_unwrap_begin", "ptycho_unwrap_iterate",
            "ptycho_unwrap_finish", "ptycho_unwrap_residues",
            "ptycho_propagate_work_words", "ptycho_propagate",
+           "ptycho_spline_work_words", "ptycho_spline_prefilter", "ptycho_warp",
+           "ptycho_moments_work_words", "ptycho_moments",
            "ptycho_last_error", "ptycho_version")
 
 if not os.path.exists(LIB_PATH):
@@ -137,6 +139,20 @@ unwrap_residues = _sig("ptycho_unwrap_residues", _i, _vp, _vp, _vp, _vp, _sz, _s
 propagate_work_words = _sig("ptycho_propagate_work_words", _sz, _vp, _sz, _sz, _i)
 #: h, planes, metrics, spec, nfield, zl, nplane, q0, method, work, stream
 propagate = _sig("ptycho_propagate", _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, ctypes.c_double, _i, _vp, _vp)
+#: resampling (no handle): nimg, ny, nx, cplx -> float64 words of ``spline_prefilter``'s scratch (0: out of range)
+spline_work_words = _sig("ptycho_spline_work_words", _sz, _sz, _sz, _sz, _i)
+#: out, in, nimg, ny, nx, cplx, order, work, stream
+spline_prefilter = _sig("ptycho_spline_prefilter", _i, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp)
+#: out, coef, xf, nimg, ny, nx, oh, ow, cplx, order, flags, cval_re, cval_im, path, stream
+warp = _sig("ptycho_warp", _i, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i, _i, _i, ctypes.c_float, ctypes.c_float, _vp, _vp)
+#: nimg, ny, nx -> float64 words of ``moments``'s scratch (0: out of range)
+moments_work_words = _sig("ptycho_moments_work_words", _sz, _sz, _sz, _sz)
+#: sums, x, weight, nimg, ny, nx, cplx, which, work, stream
+moments = _sig("ptycho_moments", _i, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp)
+#: samples of a line per segment of the prefilter (PTYCHO_SPLINE_SEGMENT), the halo per order, ``warp``'s flags
+SPLINE_SEGMENT = 64
+SPLINE_HALO = {2: 12, 3: 16, 4: 28, 5: 32}
+WARP_MIRROR, WARP_GLOBAL = 1, 2
 #: ``method`` codes of ``propagate`` and the float64 words it leaves per (field, plane)
 PROPAGATE_METHODS = {"fresnel": 0, "angular": 1}
 PROPAGATE_WORDS = 8
