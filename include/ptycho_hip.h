@@ -271,6 +271,58 @@ int ptycho_unwrap_finish(float* out, double* state, const float* buf, const floa
 int ptycho_unwrap_residues(signed char* charge, long long* count, const float* phase, const float* weight, size_t ptheta,
                            size_t nz, size_t n, void* stream);
 
+/* A first look at a scan before any reconstruction (no handle; libtike.hipfft.dpc): the moments of every diffraction
+ * pattern, per-position values spread over the object grid, and the integration of a gradient field.  Every launch runs on
+ * `stream`, nothing synchronises, no float atomics and fixed summation orders: the same inputs give the same bits.
+ *   ptycho_frame_moments_work_words  float64 words of scratch that ptycho_frame_moments needs (it may be 0: pass any
+ *                          non-null pointer then; 0 also for sizes out of range).
+ *   ptycho_frame_moments   one pass over data (float32 [ptheta][nscan][ndet][ndet], DC at [0][0], any ndet >= 1).  mask:
+ *                          ndet^2 bytes in the layout of data, nonzero = measured, or NULL; an unmeasured pixel is given
+ *                          I = 0 by a select, so what data holds there never matters; a non-finite value at a measured
+ *                          pixel stays in its frame.  With k(r) = r for r < ndet - ndet / 2, else r - ndet (the signed
+ *                          frequency index), moments (float64 [ptheta][nscan][8]) <- the sums over the pixels (y, x) of a
+ *                          frame of
+ *                            0  I          3  k(y)^2 I       6  I where k(y)^2 + k(x)^2 > darkfield^2
+ *                            1  k(y) I     4  k(x)^2 I          (0 for a negative darkfield)
+ *                            2  k(x) I     5  k(y) k(x) I    7  0
+ *                          each term formed as (double) I times the integer factor and added in float64.  16-byte loads
+ *                          when ndet^2 is a multiple of 4 and data is 16-byte aligned, scalar ones otherwise: the same
+ *                          bits.  Two launches (one when the detector has at most 512 pixels).
+ *   ptycho_scan_map        values: float32 [ptheta][nscan][nval], nval in [1, 4]; keep: uint8 [ptheta][nscan], a zero byte
+ *                          excludes the position, or NULL; scan, probe, nmodes, nprb, nz, n as for ptycho_illumination.
+ *                          weight (float32 [ptheta][nz][n]) <- ptycho_illumination of the kept positions in their order,
+ *                          formed by the same kernel: the same bits.  With A, the split (sy, sx) + (fy, fx) and the taps
+ *                          w_ab of ptycho_illumination, num_c[sy+iy+a][sx+ix+b] += (w_ab A[iy][ix]) v_j[c] over the
+ *                          positions in order and the taps in the order (0,0) (0,1) (1,0) (1,1), A = sum_m (re^2 + im^2),
+ *                          every operation rounded to float32 (no fused multiply-add), and out (float32
+ *                          [ptheta][nval][nz][n]) <- num_c / weight where weight > 0, else 0 (raw != 0: num_c itself, which
+ *                          is 0 where weight is).  Both are written in full.
+ *                          A position that the illumination skips or that keep excludes adds to nothing, whatever its
+ *                          values hold.  work: float32 scratch of 2 ptheta nscan words, needed (non-null) only with keep.
+ *                          Two launches, three with keep.
+ *   ptycho_integrate_begin   ptycho_unwrap_begin with one change: the difference of the edge p -> q is not the wrapped
+ *                          phase difference but d_e = (gx_p + gx_q) / 2 if q is to the right of p, (gy_p + gy_q) / 2 if q
+ *                          is below p, in float32 with both operations rounded (gy, gx: float32 [ptheta][nz][n], the
+ *                          gradient in units per pixel along rows' index and columns' index).  Edge weights, b, D, 1 / D,
+ *                          buf, state and work are the unwrapper's, and what gy and gx hold at a pixel of weight 0 never
+ *                          matters.  Iterate with ptycho_unwrap_iterate.  Two launches.
+ *   ptycho_integrate_finish  c = sum w' [D > 0] x / sum w' [D > 0] in float64 (0 for an empty sum) -> state;
+ *                          out = x - c, formed in float64 and rounded once, where D > 0, else 0.  Three launches.
+ * PTYCHO_ERR_ARG, before any HIP call, for a null moments / data / work / weight / out / values / scan / probe / buf /
+ * state / gy / gx, a null work of ptycho_scan_map with keep, a zero size, nval outside [1, 4], nmodes < 1, a darkfield that
+ * is NaN or +Inf, and the size limits of ptycho_fit_frames (npix = ndet^2 <= 2^31 - 1), ptycho_illumination and
+ * ptycho_unwrap_begin. */
+size_t ptycho_frame_moments_work_words(size_t ptheta, size_t nscan, size_t ndet);
+int ptycho_frame_moments(double* moments, const float* data, const unsigned char* mask, double darkfield, size_t ptheta,
+                         size_t nscan, size_t ndet, double* work, void* stream);
+int ptycho_scan_map(float* weight, float* out, const float* values, const unsigned char* keep, const void* scan,
+                    const void* probe, size_t ptheta, size_t nscan, int nval, int nmodes, size_t nprb, size_t nz, size_t n,
+                    int raw, float* work, void* stream);
+int ptycho_integrate_begin(float* buf, double* state, const float* gy, const float* gx, const float* weight, size_t ptheta,
+                           size_t nz, size_t n, double* work, void* stream);
+int ptycho_integrate_finish(float* out, double* state, const float* buf, const float* weight, size_t ptheta, size_t nz,
+                            size_t n, double* work, void* stream);
+
 /* Free-space propagation of square complex fields and the figures of a focus series (libtike.hipfft.propagate).  h is
  * a handle whose ndet is the side S of the fields, as for ptycho_fft2; it supplies the twiddle table and nothing of it is
  * changed.  Any side ptycho_fft2 takes from 16 up: 16 <= S <= 1024, or 2048.  Everything runs on `stream`, nothing

@@ -53,7 +53,7 @@ int do_unwrap_begin(float* buf, double* state, const float* phase, const float* 
                     double* work, hipStream_t st) {
     const UnwGrid g = unwrap_grid(ptheta, nz, n);
     const bool vec = unwrap_vec(n, {buf, phase, weight});
-    UNW_LAUNCH(k_unwrap_setup, vec, g.tile_grid, buf, phase, weight, nz, n, g.ntx, work);
+    UNW_LAUNCH(k_unwrap_setup, vec, g.tile_grid, buf, phase, weight, nz, n, g.ntx, work, (const float*)nullptr);
     return unwrap_scalars(state, work, ptheta, g.tiles, g.tiles, 0, 0, 0.0, st);
 }
 

@@ -167,6 +167,18 @@ __device__ __forceinline__ void fit_halve(double (&f)[FitPart::kCols], const boo
     }
 }
 
+// 8 vectors of 64 lanes -> lane 8 e stores sum e to dst[e]: bits 5, 4, 3 of the lane pick the half that is kept
+__device__ __forceinline__ void fit_wave_sums(double (&f)[FitPart::kCols], const int lane, double* __restrict__ dst) {
+    fit_halve<8>(f, (lane & 32) != 0, 32);
+    fit_halve<4>(f, (lane & 16) != 0, 16);
+    fit_halve<2>(f, (lane & 8) != 0, 8);
+    double v = f[0];
+    v += __shfl_xor(v, 4);
+    v += __shfl_xor(v, 2);
+    v += __shfl_xor(v, 1);
+    if ((lane & 7) == 0) dst[lane >> 3] = v;
+}
+
 // one frame of one wave: the lane's pixels into pacc and into the eight sums, the sums over the wave, the store to dst
 template <bool PIX>
 __device__ __forceinline__ void fit_frame(const FitRaw& raw, const float s2, const bool (&meas)[FitPart::kSlots],
@@ -188,15 +200,7 @@ __device__ __forceinline__ void fit_frame(const FitRaw& raw, const float s2, con
             pacc[3][q] += (double)tm[3];
         }
     }
-    // 8 vectors of 64 lanes -> lane 8 e holds sum e: bits 5, 4, 3 of the lane pick the half that is kept
-    fit_halve<8>(f, (lane & 32) != 0, 32);
-    fit_halve<4>(f, (lane & 16) != 0, 16);
-    fit_halve<2>(f, (lane & 8) != 0, 8);
-    double v = f[0];
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 1);
-    if ((lane & 7) == 0) dst[lane >> 3] = v;
+    fit_wave_sums(f, lane, dst);
 }
 
 // grid (ntiles, nranges, ptheta), 256 threads

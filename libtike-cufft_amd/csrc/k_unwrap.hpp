@@ -7,7 +7,10 @@
 //
 //   k_unwrap_setup    one 256-thread workgroup per 64 x 16 tile, a thread owns four pixels of one row.  phi and the
 //                     effective weight w' of the tile and of its one-pixel halo (no corners) go through LDS; per pixel
-//                     b -> r, D -> 1 / D, x = 0, p = r / D, and the tile's part of rz0 = r . z.
+//                     b -> r, D -> 1 / D, x = 0, p = r / D, and the tile's part of rz0 = r . z.  Where the difference
+//                     d_e of an edge comes from is a template parameter: the wrapped difference of a phase
+//                     (UnwPhaseSrc, the unwrapper) or the mean of a gradient field at the edge's two ends (UnwGradSrc,
+//                     ptycho_integrate_begin of k_dpc.hpp); everything else is shared.
 //   k_unwrap_apply    the same tile.  The direction of this iteration, p = z + beta p_old (beta = 0 in the first), is
 //                     formed on the load for the tile AND its halo from r, 1 / D and the previous direction -- the same
 //                     expression on the same operands wherever a pixel is formed, so the same bits --, written for the
@@ -70,6 +73,9 @@ PTY_HD bool unwrap_halo(const int tid, const int by, const int bx, int& y, int& 
 PTY_HD int unwrap_slot(const int y, const int x, const int by, const int bx) {
     return (y - by * kUnwTileH + 1) * kUnwLdsW + (x - bx * kUnwTileW + 1);
 }
+// the plane of a gradient field (0: gy, along the row index; 1: gx, along the column index) that gives the difference of
+// an edge: gy for an edge between a pixel and the one below it (vertical), gx for one to the right
+PTY_HD int unwrap_grad_field(const bool vertical) { return vertical ? 0 : 1; }
 
 #if defined(__HIPCC__)
 
@@ -128,31 +134,60 @@ __device__ __forceinline__ void unwrap_store4(float* __restrict__ dst, const siz
     }
 }
 
-// grid (tiles, ptheta), 256 threads
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_unwrap_setup(float* __restrict__ buf, const float* __restrict__ phase,
+// Where k_unwrap_setup takes the difference d_e of an edge from: kFields planes [ptheta][nz][n] that go through LDS with
+// the tile, and diff(l, a, b, vertical), the difference of the edge from slot a to slot b -- b to the right of a, or
+// below it (vertical) --, every operation rounded to float32.
+//   UnwPhaseSrc  the wrapped difference of a phase, W(phi_b - phi_a): ptycho_unwrap_begin
+//   UnwGradSrc   the mean of a gradient field at the two ends, (g_a + g_b) / 2 of gx along a row and of gy along a column:
+//                ptycho_integrate_begin
+struct UnwPhaseSrc {
+    static constexpr int kFields = 1;
+    __device__ __forceinline__ static float diff(const float (&l)[kFields][kUnwLdsH * kUnwLdsW], const int a, const int b,
+                                                 const bool /*vertical*/) {
+        return unwrap_W(__fsub_rn(l[0][b], l[0][a]));
+    }
+};
+struct UnwGradSrc {
+    static constexpr int kFields = 2;   // gy, gx
+    __device__ __forceinline__ static float diff(const float (&l)[kFields][kUnwLdsH * kUnwLdsW], const int a, const int b,
+                                                 const bool vertical) {
+#pragma clang fp contract(off)
+        const int e = unwrap_grad_field(vertical);
+        return 0.5f * (l[e][a] + l[e][b]);
+    }
+};
+
+// grid (tiles, ptheta), 256 threads; f0, f1: the planes of Src (f1 is read only when Src has two)
+template <bool VEC, class Src = UnwPhaseSrc>
+__global__ __launch_bounds__(256) void k_unwrap_setup(float* __restrict__ buf, const float* __restrict__ f0,
                                                       const float* __restrict__ weight, const int nz, const int n,
-                                                      const int ntx, double* __restrict__ work) {
-    __shared__ float l_f[kUnwLdsH * kUnwLdsW], l_w[kUnwLdsH * kUnwLdsW];
+                                                      const int ntx, double* __restrict__ work,
+                                                      const float* __restrict__ f1) {
+    __shared__ float l_f[Src::kFields][kUnwLdsH * kUnwLdsW], l_w[kUnwLdsH * kUnwLdsW];
     __shared__ double part[4];
     const int tid = threadIdx.x, t = blockIdx.y;
     const UnwTile u = unwrap_tile(ntx, nz);
     const size_t plane = (size_t)nz * (size_t)n;
-    const float* ph = phase + (size_t)t * plane;
     const float* wt = weight ? weight + (size_t)t * plane : nullptr;
     float* base = buf + (size_t)t * kUnwPlanes * plane;
     const int have = !u.row ? 0 : (n - u.x >= kUnwVec ? kUnwVec : (n - u.x > 0 ? n - u.x : 0));
     const size_t idx = (size_t)u.y * (size_t)n + (size_t)u.x;
     {
-        float f[kUnwVec] = {0.0f, 0.0f, 0.0f, 0.0f}, w[kUnwVec] = {0.0f, 0.0f, 0.0f, 0.0f};
+        float f[Src::kFields][kUnwVec], w[kUnwVec] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int e = 0; e < Src::kFields; ++e)
+#pragma unroll
+            for (int k = 0; k < kUnwVec; ++k) f[e][k] = 0.0f;
         if (have > 0) {
-            unwrap_load4<VEC>(f, ph, idx, have);
+#pragma unroll
+            for (int e = 0; e < Src::kFields; ++e) unwrap_load4<VEC>(f[e], (e == 0 ? f0 : f1) + (size_t)t * plane, idx, have);
             if (wt) unwrap_load4<VEC>(w, wt, idx, have);
         }
         const int s = unwrap_slot(u.y, u.x, u.by, u.bx);
 #pragma unroll
         for (int k = 0; k < kUnwVec; ++k) {
-            l_f[s + k] = f[k];
+#pragma unroll
+            for (int e = 0; e < Src::kFields; ++e) l_f[e][s + k] = f[e][k];
             l_w[s + k] = k < have ? (wt ? unwrap_wsel(w[k]) : 1.0f) : 0.0f;
         }
         int hy, hx;
@@ -160,7 +195,8 @@ __global__ __launch_bounds__(256) void k_unwrap_setup(float* __restrict__ buf, c
             const bool in = unwrap_inside(hy, hx, nz, n);
             const size_t hi = (size_t)(in ? hy : 0) * (size_t)n + (size_t)(in ? hx : 0);
             const int hs = unwrap_slot(hy, hx, u.by, u.bx);
-            l_f[hs] = in ? ph[hi] : 0.0f;
+#pragma unroll
+            for (int e = 0; e < Src::kFields; ++e) l_f[e][hs] = in ? (e == 0 ? f0 : f1)[(size_t)t * plane + hi] : 0.0f;
             l_w[hs] = in ? unwrap_weight(wt, hi) : 0.0f;
         }
     }
@@ -171,15 +207,16 @@ __global__ __launch_bounds__(256) void k_unwrap_setup(float* __restrict__ buf, c
         const int s = unwrap_slot(u.y, u.x, u.by, u.bx);
 #pragma unroll
         for (int k = 0; k < kUnwVec; ++k) {
-            const float fc = l_f[s + k], wc = l_w[s + k];
+            const int c = s + k;
+            const float wc = l_w[c];
             // edges in the order left, right, up, down; an edge of weight 0 contributes exactly 0 (a select)
-            const float wl = fminf(wc, l_w[s + k - 1]), wr = fminf(wc, l_w[s + k + 1]);
-            const float wu = fminf(wc, l_w[s + k - kUnwLdsW]), wd = fminf(wc, l_w[s + k + kUnwLdsW]);
+            const float wl = fminf(wc, l_w[c - 1]), wr = fminf(wc, l_w[c + 1]);
+            const float wu = fminf(wc, l_w[c - kUnwLdsW]), wd = fminf(wc, l_w[c + kUnwLdsW]);
             float b = 0.0f, D = 0.0f;
-            if (wl > 0.0f) { b = __fadd_rn(b, __fmul_rn(wl, unwrap_W(__fsub_rn(fc, l_f[s + k - 1])))); D = __fadd_rn(D, wl); }
-            if (wr > 0.0f) { b = __fsub_rn(b, __fmul_rn(wr, unwrap_W(__fsub_rn(l_f[s + k + 1], fc)))); D = __fadd_rn(D, wr); }
-            if (wu > 0.0f) { b = __fadd_rn(b, __fmul_rn(wu, unwrap_W(__fsub_rn(fc, l_f[s + k - kUnwLdsW])))); D = __fadd_rn(D, wu); }
-            if (wd > 0.0f) { b = __fsub_rn(b, __fmul_rn(wd, unwrap_W(__fsub_rn(l_f[s + k + kUnwLdsW], fc)))); D = __fadd_rn(D, wd); }
+            if (wl > 0.0f) { b = __fadd_rn(b, __fmul_rn(wl, Src::diff(l_f, c - 1, c, false))); D = __fadd_rn(D, wl); }
+            if (wr > 0.0f) { b = __fsub_rn(b, __fmul_rn(wr, Src::diff(l_f, c, c + 1, false))); D = __fadd_rn(D, wr); }
+            if (wu > 0.0f) { b = __fadd_rn(b, __fmul_rn(wu, Src::diff(l_f, c - kUnwLdsW, c, true))); D = __fadd_rn(D, wu); }
+            if (wd > 0.0f) { b = __fsub_rn(b, __fmul_rn(wd, Src::diff(l_f, c, c + kUnwLdsW, true))); D = __fadd_rn(D, wd); }
             r[k] = b;
             mi[k] = D > 0.0f ? __fdiv_rn(1.0f, D) : 0.0f;
             z[k] = __fmul_rn(mi[k], b);

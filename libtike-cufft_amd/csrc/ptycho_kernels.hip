@@ -53,6 +53,7 @@
 #include "k_prepare.hpp"
 #include "k_unwrap.hpp"
 #include "k_resample.hpp"
+#include "k_dpc.hpp"
 
 using namespace pty;
 
@@ -80,6 +81,7 @@ namespace {
 #include "host_unwrap.hpp"
 #include "host_propagate.hpp"
 #include "host_resample.hpp"
+#include "host_dpc.hpp"
 
 extern "C" {
 
@@ -708,6 +710,58 @@ int ptycho_unwrap_residues(signed char* charge, long long* count, const float* p
     if (!count || !phase) return fail(PTYCHO_ERR_ARG, "count and phase must not be null");
     if (int rc = unwrap_check_sizes(ptheta, nz, n)) return rc;
     return do_unwrap_residues(charge, count, phase, weight, (int)ptheta, (int)nz, (int)n, (hipStream_t)stream);
+}
+
+// ---- first look: frame moments, scan map, gradient integration (k_dpc.hpp, libtike.hipfft.dpc): no handle --------------------
+static bool moments_sizes_ok(size_t ptheta, size_t nscan, size_t ndet) {
+    return ndet >= 1 && ndet <= 46340 && fit_sizes_ok(ptheta, nscan, ndet * ndet);   // ndet^2 <= 2^31 - 1
+}
+
+size_t ptycho_frame_moments_work_words(size_t ptheta, size_t nscan, size_t ndet) {
+    return frame_work_words<MomPart>(moments_sizes_ok(ptheta, nscan, ndet), ptheta, nscan, ndet * ndet);
+}
+
+int ptycho_frame_moments(double* moments, const float* data, const unsigned char* mask, double darkfield, size_t ptheta,
+                         size_t nscan, size_t ndet, double* work, void* stream) {
+    if (!moments || !data || !work) return fail(PTYCHO_ERR_ARG, "moments, data and work must not be null");
+    if (ptheta == 0 || nscan == 0 || ndet == 0) return fail(PTYCHO_ERR_ARG, "all sizes must be positive");
+    if (ptheta > kFitMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
+    if (darkfield != darkfield || darkfield == INFINITY) return fail(PTYCHO_ERR_ARG, "darkfield must be a finite radius, or negative for none");
+    if (!moments_sizes_ok(ptheta, nscan, ndet) || (ptheta * nscan * MomPart::kCols) / 256 + 2 > 0x7fffffffull)
+        return fail(PTYCHO_ERR_ARG, "nscan, ndet or their product with ptheta too large for one launch");
+    return do_frame_moments(moments, data, mask, darkfield, (long long)ptheta, (long long)nscan, (long long)ndet, work,
+                            (hipStream_t)stream);
+}
+
+int ptycho_scan_map(float* weight, float* out, const float* values, const unsigned char* keep, const void* scan,
+                    const void* probe, size_t ptheta, size_t nscan, int nval, int nmodes, size_t nprb, size_t nz, size_t n,
+                    int raw, float* work, void* stream) {
+    if (!weight || !out || !values || !scan || !probe)
+        return fail(PTYCHO_ERR_ARG, "weight, out, values, scan and probe must not be null");
+    if (keep && !work) return fail(PTYCHO_ERR_ARG, "work must not be null when keep is given");
+    if (ptheta == 0 || nscan == 0 || nprb == 0 || nz == 0 || n == 0) return fail(PTYCHO_ERR_ARG, "all sizes must be positive");
+    if (nval < 1 || nval > kMapMaxVal) return fail(PTYCHO_ERR_ARG, "nval must be in [1, 4]");
+    if (nmodes < 1) return fail(PTYCHO_ERR_ARG, "nmodes must be at least 1");
+    if (ptheta > kGaugeMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
+    if (nz > kGaugeMaxSide || n > kGaugeMaxSide || nprb > kGaugeMaxSide || nscan > 0x7fffffffull ||
+        (nz + kIllTileH - 1) / kIllTileH > 65535 || (ptheta * nscan + 255) / 256 > 0x7fffffffull)
+        return fail(PTYCHO_ERR_ARG, "nz, n, nprb or nscan too large for one launch");
+    return do_scan_map(weight, out, values, keep, (const float*)scan, (const c32*)probe, (int)ptheta, (int)nscan, nval, nmodes,
+                       (int)nprb, (int)nz, (int)n, raw != 0, work, (hipStream_t)stream);
+}
+
+int ptycho_integrate_begin(float* buf, double* state, const float* gy, const float* gx, const float* weight, size_t ptheta,
+                           size_t nz, size_t n, double* work, void* stream) {
+    if (!buf || !state || !gy || !gx || !work) return fail(PTYCHO_ERR_ARG, "buf, state, gy, gx and work must not be null");
+    if (int rc = unwrap_check_sizes(ptheta, nz, n)) return rc;
+    return do_integrate_begin(buf, state, gy, gx, weight, (int)ptheta, (int)nz, (int)n, work, (hipStream_t)stream);
+}
+
+int ptycho_integrate_finish(float* out, double* state, const float* buf, const float* weight, size_t ptheta, size_t nz,
+                            size_t n, double* work, void* stream) {
+    if (!out || !state || !buf || !work) return fail(PTYCHO_ERR_ARG, "out, state, buf and work must not be null");
+    if (int rc = unwrap_check_sizes(ptheta, nz, n)) return rc;
+    return do_integrate_finish(out, state, buf, weight, (int)ptheta, (int)nz, (int)n, work, (hipStream_t)stream);
 }
 
 // ---- free-space propagation and focus-series figures (k_propagate.hpp, libtike.hipfft.propagate) -------------------------

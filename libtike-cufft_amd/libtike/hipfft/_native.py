@@ -33,6 +33,8 @@ SYMBOLS = ("ptycho_create", "ptycho_free", "ptycho_destroy", "ptycho_get",
            "ptycho_prepare_work_words", "ptycho_prepare_frames",
            "ptycho_unwrap_work_words", "ptycho_unwrap_buffer_floats", "ptycho_unwrap_begin", "ptycho_unwrap_iterate",
            "ptycho_unwrap_finish", "ptycho_unwrap_residues",
+           "ptycho_frame_moments_work_words", "ptycho_frame_moments", "ptycho_scan_map",
+           "ptycho_integrate_begin", "ptycho_integrate_finish",
            "ptycho_propagate_work_words", "ptycho_propagate",
            "ptycho_spline_work_words", "ptycho_spline_prefilter", "ptycho_warp",
            "ptycho_moments_work_words", "ptycho_moments",
@@ -135,6 +137,18 @@ unwrap_iterate = _sig("ptycho_unwrap_iterate", _i, _vp, _vp, _vp, _sz, _sz, _sz,
 unwrap_finish = _sig("ptycho_unwrap_finish", _i, _vp, _vp, _vp, _vp, _vp, _i, _sz, _sz, _sz, _vp, _vp)
 #: charge, count, phase, weight, ptheta, nz, n, stream
 unwrap_residues = _sig("ptycho_unwrap_residues", _i, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp)
+#: first look (no handle): ptheta, nscan, ndet -> float64 words of ``frame_moments``'s scratch (0: out of range)
+frame_moments_work_words = _sig("ptycho_frame_moments_work_words", _sz, _sz, _sz, _sz)
+#: moments, data, mask, darkfield, ptheta, nscan, ndet, work, stream
+frame_moments = _sig("ptycho_frame_moments", _i, _vp, _vp, _vp, ctypes.c_double, _sz, _sz, _sz, _vp, _vp)
+#: weight, out, values, keep, scan, probe, ptheta, nscan, nval, nmodes, nprb, nz, n, raw, work, stream
+scan_map = _sig("ptycho_scan_map", _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _i, _sz, _sz, _sz, _i, _vp, _vp)
+#: buf, state, gy, gx, weight, ptheta, nz, n, work, stream (buf, state, work: the unwrapper's)
+integrate_begin = _sig("ptycho_integrate_begin", _i, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp)
+#: out, state, buf, weight, ptheta, nz, n, work, stream
+integrate_finish = _sig("ptycho_integrate_finish", _i, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp)
+#: channels of one ``scan_map`` call
+SCAN_MAP_MAX_VALUES = 4
 #: propagation (handle of ndet = S): h, nfield, nplane, planes_wanted -> float64 words of ``propagate``'s scratch
 propagate_work_words = _sig("ptycho_propagate_work_words", _sz, _vp, _sz, _sz, _i)
 #: h, planes, metrics, spec, nfield, zl, nplane, q0, method, work, stream
