@@ -12,9 +12,7 @@ int do_frame_moments(double* moments, const float* data, const unsigned char* ma
     const MomArgs a{f.fpart, data, mask, darkfield >= 0.0 ? darkfield * darkfield : -1.0, npix, f.p.nwt, (int)nscan,
                     (int)f.p.flen, (int)ndet};
     // 16-byte loads: every frame starts on a multiple of four pixels and the array on 16 bytes
-    if (npix % MomPart::kLanePix == 0 && aligned16(data)) hipLaunchKernelGGL(k_frame_moments<true>, f.grid(), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_frame_moments<false>, f.grid(), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
+    VEC_LAUNCH(k_frame_moments, npix % MomPart::kLanePix == 0 && aligned16(data), f.grid(), st, a);
     return f.fold(k_frame_moments_fold, 0, st);
 }
 
@@ -30,7 +28,7 @@ int do_scan_map(float* weight, float* out, const float* values, const unsigned c
         scan = work;
     }
     if (int rc = do_illumination(weight, scan, probe, ptheta, nscan, nmodes, nprb, nz, n, st)) return rc;
-    const dim3 grid((unsigned)((n + kIllTileW - 1) / kIllTileW), (unsigned)((nz + kIllTileH - 1) / kIllTileH), (unsigned)ptheta);
+    const dim3 grid = illum_grid(ptheta, nz, n);
 #define MAP_LAUNCH(NV) \
     hipLaunchKernelGGL(k_scan_map<NV>, grid, dim3(256), 0, st, out, (const float*)weight, values, scan, probe, nscan, nmodes, nprb, nz, n, raw)
     switch (nval) {
@@ -43,13 +41,6 @@ int do_scan_map(float* weight, float* out, const float* values, const unsigned c
     HIP_TRY(hipGetLastError());
     return PTYCHO_OK;
 }
-
-#define DPC_LAUNCH(kernel, vec, grid, ...)                                                          \
-    do {                                                                                            \
-        if (vec) hipLaunchKernelGGL(kernel<true>, grid, dim3(256), 0, st, __VA_ARGS__);             \
-        else hipLaunchKernelGGL(kernel<false>, grid, dim3(256), 0, st, __VA_ARGS__);                \
-        HIP_TRY(hipGetLastError());                                                                 \
-    } while (0)
 
 // the unwrapper's setup with the gradient as the source of the edge differences, and its fold: two launches
 int do_integrate_begin(float* buf, double* state, const float* gy, const float* gx, const float* weight, int ptheta, int nz,
@@ -68,13 +59,11 @@ int do_integrate_finish(float* out, double* state, const float* buf, const float
     const UnwGrid g = unwrap_grid(ptheta, nz, n);
     const bool vec = unwrap_vec(n, {out, buf, weight});
     const size_t plane = (size_t)nz * (size_t)n;
-    DPC_LAUNCH(k_integrate_offset, vec, g.flat_grid, buf, weight, plane, g.tiles, work);
+    VEC_LAUNCH(k_integrate_offset, vec, g.flat_grid, st, buf, weight, plane, g.tiles, work);
     hipLaunchKernelGGL(k_integrate_mean, dim3((unsigned)ptheta), dim3(256), 0, st, state, (const double*)work, g.flat, g.tiles);
     HIP_TRY(hipGetLastError());
-    DPC_LAUNCH(k_integrate_finish, vec, g.flat_grid, out, (const double*)state, buf, plane);
+    VEC_LAUNCH(k_integrate_finish, vec, g.flat_grid, st, out, (const double*)state, buf, plane);
     return PTYCHO_OK;
 }
-
-#undef DPC_LAUNCH
 
 }  // namespace

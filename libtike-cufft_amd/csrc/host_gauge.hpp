@@ -6,10 +6,14 @@ namespace {
 
 static_assert(PTYCHO_GAUGE_WORK_PER_ANGLE == kGaugeMaxBlocks * kGaugeStride, "work rows of ptycho_gauge_fit");
 
+// one workgroup per 64 x 16 tile of every angle's object: the grid of k_illumination and of k_scan_map
+dim3 illum_grid(int ptheta, int nz, int n) {
+    return dim3((unsigned)((n + kIllTileW - 1) / kIllTileW), (unsigned)((nz + kIllTileH - 1) / kIllTileH), (unsigned)ptheta);
+}
+
 int do_illumination(float* out, const float* scan, const c32* probe, int ptheta, int nscan, int nmodes, int nprb, int nz,
                     int n, hipStream_t st) {
-    const dim3 grid((unsigned)((n + kIllTileW - 1) / kIllTileW), (unsigned)((nz + kIllTileH - 1) / kIllTileH), (unsigned)ptheta);
-    hipLaunchKernelGGL(k_illumination, grid, dim3(256), 0, st, out, scan, probe, nscan, nmodes, nprb, nz, n);
+    hipLaunchKernelGGL(k_illumination, illum_grid(ptheta, nz, n), dim3(256), 0, st, out, scan, probe, nscan, nmodes, nprb, nz, n);
     HIP_TRY(hipGetLastError());
     return PTYCHO_OK;
 }

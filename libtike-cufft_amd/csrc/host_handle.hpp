@@ -88,6 +88,15 @@ int fail(int code, const std::string& msg) {
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// launch of a 256-thread kernel template <bool VEC> on the stream st: kernel<true> (16-byte accesses) where vec holds,
+// else kernel<false>; returns from the calling launcher on a launch error (HIP_TRY)
+#define VEC_LAUNCH(kernel, vec, grid, st, ...)                                                      \
+    do {                                                                                            \
+        if (vec) hipLaunchKernelGGL(kernel<true>, grid, dim3(256), 0, st, __VA_ARGS__);             \
+        else hipLaunchKernelGGL(kernel<false>, grid, dim3(256), 0, st, __VA_ARGS__);                \
+        HIP_TRY(hipGetLastError());                                                                 \
+    } while (0)
+
 // the host's half of a FramePart (frame_part.hpp) for checked sizes: the plan and the launch grid of the pass, where the
 // pass writes (fpart, ppart), and after the pass the fold of whatever it left in work (nothing: one wave tile and one range)
 template <class Part>

@@ -34,13 +34,6 @@ UnwGrid unwrap_grid(int ptheta, int nz, int n) {
     return g;
 }
 
-#define UNW_LAUNCH(kernel, vec, grid, ...)                                                          \
-    do {                                                                                            \
-        if (vec) hipLaunchKernelGGL(kernel<true>, grid, dim3(256), 0, st, __VA_ARGS__);             \
-        else hipLaunchKernelGGL(kernel<false>, grid, dim3(256), 0, st, __VA_ARGS__);                \
-        HIP_TRY(hipGetLastError());                                                                 \
-    } while (0)
-
 int unwrap_scalars(double* state, const double* work, int ptheta, long long rows, long long tiles, int stage, int maxiter,
                    double tol, hipStream_t st) {
     hipLaunchKernelGGL(k_unwrap_scalars, dim3((unsigned)ptheta), dim3(256), 0, st, state, work, rows, tiles, stage, maxiter, tol);
@@ -53,7 +46,7 @@ int do_unwrap_begin(float* buf, double* state, const float* phase, const float* 
                     double* work, hipStream_t st) {
     const UnwGrid g = unwrap_grid(ptheta, nz, n);
     const bool vec = unwrap_vec(n, {buf, phase, weight});
-    UNW_LAUNCH(k_unwrap_setup, vec, g.tile_grid, buf, phase, weight, nz, n, g.ntx, work, (const float*)nullptr);
+    VEC_LAUNCH(k_unwrap_setup, vec, g.tile_grid, st, buf, phase, weight, nz, n, g.ntx, work, (const float*)nullptr);
     return unwrap_scalars(state, work, ptheta, g.tiles, g.tiles, 0, 0, 0.0, st);
 }
 
@@ -65,9 +58,9 @@ int do_unwrap_iterate(float* buf, double* state, const float* weight, int ptheta
     const bool vec = unwrap_vec(n, {buf, weight});
     const size_t plane = (size_t)nz * (size_t)n;
     for (int i = 0; i < niter; ++i) {
-        UNW_LAUNCH(k_unwrap_apply, vec, g.tile_grid, buf, (const double*)state, weight, nz, n, g.ntx, maxiter, work);
+        VEC_LAUNCH(k_unwrap_apply, vec, g.tile_grid, st, buf, (const double*)state, weight, nz, n, g.ntx, maxiter, work);
         if (int rc = unwrap_scalars(state, work, ptheta, g.tiles, g.tiles, 1, maxiter, tol, st)) return rc;
-        UNW_LAUNCH(k_unwrap_update, vec, g.flat_grid, buf, (const double*)state, plane, g.tiles, work);
+        VEC_LAUNCH(k_unwrap_update, vec, g.flat_grid, st, buf, (const double*)state, plane, g.tiles, work);
         if (int rc = unwrap_scalars(state, work, ptheta, g.flat, g.tiles, 2, maxiter, tol, st)) return rc;
     }
     return unwrap_scalars(state, work, ptheta, 0, g.tiles, 4, maxiter, tol, st);
@@ -79,9 +72,9 @@ int do_unwrap_finish(float* out, double* state, const float* buf, const float* p
     const UnwGrid g = unwrap_grid(ptheta, nz, n);
     const bool vec = unwrap_vec(n, {out, buf, phase, weight});
     const size_t plane = (size_t)nz * (size_t)n;
-    UNW_LAUNCH(k_unwrap_offset, vec, g.flat_grid, buf, phase, weight, plane, g.tiles, work);
+    VEC_LAUNCH(k_unwrap_offset, vec, g.flat_grid, st, buf, phase, weight, plane, g.tiles, work);
     if (int rc = unwrap_scalars(state, work, ptheta, g.flat, g.tiles, 3, 0, 0.0, st)) return rc;
-    UNW_LAUNCH(k_unwrap_finish, vec, g.flat_grid, out, (const double*)state, buf, phase, plane, congruent);
+    VEC_LAUNCH(k_unwrap_finish, vec, g.flat_grid, st, out, (const double*)state, buf, phase, plane, congruent);
     return PTYCHO_OK;
 }
 
@@ -94,7 +87,5 @@ int do_unwrap_residues(signed char* charge, long long* count, const float* phase
     HIP_TRY(hipGetLastError());
     return PTYCHO_OK;
 }
-
-#undef UNW_LAUNCH
 
 }  // namespace

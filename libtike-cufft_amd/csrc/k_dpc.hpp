@@ -13,19 +13,22 @@
 //                       over the wave (fit_wave_sums, k_fit.hpp).  An unmeasured pixel gets I = 0 by a select.
 //   k_frame_moments_fold  adds the wave tiles of every frame in index order.
 //   k_scan_keep         a copy of scan with NaN at the positions that keep excludes: every walk skips them.
-//   k_scan_map          k_illumination's tile, staging and walk (k_gauge.hpp) over its index helpers, with the NVAL values
-//                       of every position beside the packed list in LDS: per channel num += (w_ab A) v_j, every
-//                       operation rounded, taps outside the probe dropped by a select; out = num / weight where
-//                       weight > 0, else 0.  The weight is not formed again: the launcher runs k_illumination itself on
-//                       the same scan first and this kernel reads its result -- the compiler fuses some of that kernel's
-//                       multiply-adds and not others, so only the kernel itself gives ptycho_illumination's bits.
+//   k_scan_map          k_illumination's tile and walk (k_gauge.hpp) over its index helpers and its staging itself
+//                       (illum_stage), with the NVAL values of every position stored beside the packed list in LDS at the
+//                       slot that illum_stage returns: per channel num += (w_ab A) v_j, every operation rounded, taps
+//                       outside the probe dropped by a select; out = num / weight where weight > 0, else 0.  The weight is
+//                       not formed again: the launcher runs k_illumination itself on the same scan first and this kernel
+//                       reads its result -- the compiler fuses some of that kernel's multiply-adds and not others, so only
+//                       the kernel itself gives ptycho_illumination's bits, which is also why the two kernels share the
+//                       staging and not the walk (k_gauge.hpp's header).  map_amp2 / illum_amp2 stay two functions: their
+//                       contraction differs on purpose.
 //   k_integrate_offset  flat: parts of sum w' [D > 0] x and sum w' [D > 0] in float64.
 //   k_integrate_mean    one workgroup per angle: adds the parts in index order, c = sum w' x / sum w' -> state.
 //   k_integrate_finish  flat: out = x - c where D > 0, else 0.
 // The setup of the integration is k_unwrap_setup<VEC, UnwGradSrc> (k_unwrap.hpp) and its iterations are the unwrapper's.
 //
 // The index logic (moment_k, the partition, the walk's helpers, the tile / halo slots) is plain C++: tests/test_dpc_cpu.py
-// builds host_dpc.cpp with the host compiler and walks it.
+// builds host_dpc.cpp with the host compiler and walks it (frame_part_walk.hpp, illum_walk.hpp, unwrap_walk.hpp).
 #pragma once
 
 #include "frame_part.hpp"
@@ -191,8 +194,8 @@ __global__ __launch_bounds__(256) void k_scan_keep(float* __restrict__ out, cons
     out[2 * i + 1] = on ? scan[2 * i + 1] : NAN;
 }
 
-// grid (ceil(n / 64), ceil(nz / 16), ptheta), 256 threads: k_illumination's tile, staging and walk (k_gauge.hpp) over its
-// index helpers.  weight: [ptheta][nz][n], written by the launch of k_illumination on the same scan before this one;
+// grid (ceil(n / 64), ceil(nz / 16), ptheta), 256 threads: k_illumination's tile and walk (k_gauge.hpp) over its index
+// helpers and illum_stage.  weight: [ptheta][nz][n], written by the launch of k_illumination on the same scan before this one;
 // out: [ptheta][NVAL][nz][n], num / weight or, with raw, num itself; values: [ptheta][nscan][NVAL], staged beside the packed list
 template <int NVAL>
 __global__ __launch_bounds__(256) void k_scan_map(float* __restrict__ out, const float* __restrict__ weight,
@@ -214,28 +217,9 @@ __global__ __launch_bounds__(256) void k_scan_map(float* __restrict__ out, const
 #pragma unroll
         for (int c = 0; c < NVAL; ++c) num[r][c] = 0.0f;
     for (int c0 = 0; c0 < nscan; c0 += kIllChunk) {
-        __syncthreads();   // the list of the chunk before has been walked by every wave
-        int sy = 0, sx = 0;
-        float fy = 0.0f, fx = 0.0f;
-        bool take = false;
-        if (tid < kIllChunk && c0 + tid < nscan) {
-            const size_t p = (size_t)(c0 + tid);
-            const bool vy = illum_split(sc[2 * p], sy, fy), vx = illum_split(sc[2 * p + 1], sx, fx);
-            take = vy && vx && illum_overlaps(sy, sx, nprb, y0, x0, nz, n);
-        }
-        const unsigned long long m = __ballot(take);
-        if (lane == 0) l_cnt[wave] = __popcll(m);
-        __syncthreads();
-        int base = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int c = l_cnt[w];
-            base += w < wave ? c : 0;
-            total += c;
-        }
-        if (take) {   // packed in position order
-            const int at = base + __popcll(m & ((1ull << lane) - 1ull));
-            l_sy[at] = sy; l_sx[at] = sx; l_fy[at] = fy; l_fx[at] = fx;
+        int at;
+        const int total = illum_stage(sc, nscan, c0, nprb, y0, x0, nz, n, l_sy, l_sx, l_fy, l_fx, l_cnt, at);
+        if (at >= 0) {   // the position's values beside it in the packed list
 #pragma unroll
             for (int c = 0; c < NVAL; ++c) l_v[at][c] = vals[(size_t)(c0 + tid) * NVAL + c];
         }

@@ -20,8 +20,19 @@
 //                    the phase formed in float64 turns and reduced before sincospi.
 //   k_gauge_apply    one thread per element, the phase as in pass 2.
 //
-// The index logic of k_illumination (split, overlap test, tap -> probe index) is plain C++: tests/test_gauge_cpu.py builds
-// host_gauge.cpp with the host compiler and checks that every (position, tap, pixel) contribution is visited exactly once.
+// The staging of a chunk (barrier, split, overlap test, ballot, wave totals, packed store) is illum_stage, which
+// k_scan_map (k_dpc.hpp) calls too.  Nothing else of k_illumination is shared with that kernel, on purpose: its low bits are
+// whatever the compiler makes of its multiply-adds -- 6 packed FMAs and two packed multiply / add pairs left unfused in
+// today's build -- and moving the walk of the packed list into a shared function (the taps as a lambda, the LDS arrays in a
+// struct or as pointers, the weights formed inside or outside) made it 8 packed FMAs, i.e. another rounding; sharing the
+// column gather (the v[k] / l[k] loads with __shfl_up) changed the float sequence as well.  With illum_stage alone the
+// ordered list of float instructions, the registers, LDS and occupancy are those of the kernel written out in full
+// (profiles/r18/walks_refactor.txt).  So: share what touches no float, and compare the listing after any change here
+// (tools/isa_compare.py --float=k_illumination).
+//
+// The index logic of k_illumination (split, overlap test, tap -> probe index) is plain C++: illum_walk.hpp walks it on the
+// host as the kernels do, and tests/test_gauge_cpu.py builds host_gauge.cpp with the host compiler and checks that every
+// (position, tap, pixel) contribution is visited exactly once.
 #pragma once
 
 #include <cmath>
@@ -84,6 +95,42 @@ __device__ __forceinline__ float illum_amp2(const c32* __restrict__ prb, const i
     return a;
 }
 
+// One chunk of kIllChunk positions from c0 on, staged for the tile at (y0, x0): thread tid < kIllChunk splits position
+// c0 + tid and tests its footprint against the tile, and the survivors are packed IN POSITION ORDER into l_sy / l_sx /
+// l_fy / l_fx (ballot + popcount within a wave, the wave totals through l_cnt).  Returns the number packed; at: the slot
+// of the thread's own position, -1 if it was dropped -- a kernel that carries more per position stores it at that slot.
+// Opens with the barrier that ends the walk of the chunk before; the caller places the barrier that ends the staging.
+__device__ __forceinline__ int illum_stage(const float* __restrict__ sc, const int nscan, const int c0, const int nprb,
+                                           const int y0, const int x0, const int nz, const int n, int* l_sy, int* l_sx,
+                                           float* l_fy, float* l_fx, int* l_cnt, int& at) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __syncthreads();   // the list of the chunk before has been walked by every wave
+    int sy = 0, sx = 0;
+    float fy = 0.0f, fx = 0.0f;
+    bool keep = false;
+    if (tid < kIllChunk && c0 + tid < nscan) {
+        const size_t p = (size_t)(c0 + tid);
+        const bool vy = illum_split(sc[2 * p], sy, fy), vx = illum_split(sc[2 * p + 1], sx, fx);
+        keep = vy && vx && illum_overlaps(sy, sx, nprb, y0, x0, nz, n);
+    }
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) l_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int c = l_cnt[w];
+        base += w < wave ? c : 0;
+        total += c;
+    }
+    at = -1;
+    if (keep) {
+        at = base + __popcll(m & ((1ull << lane) - 1ull));
+        l_sy[at] = sy; l_sx[at] = sx; l_fy[at] = fy; l_fx[at] = fx;
+    }
+    return total;
+}
+
 // grid (ceil(n / 64), ceil(nz / 16), ptheta), 256 threads
 __global__ __launch_bounds__(256) void k_illumination(float* __restrict__ out, const float* __restrict__ scan,
                                                       const c32* __restrict__ probe, const int nscan, const int nmodes,
@@ -98,29 +145,8 @@ __global__ __launch_bounds__(256) void k_illumination(float* __restrict__ out, c
     const c32* prb = probe + (size_t)t * nmodes * nprb * nprb;
     float acc[kIllRows] = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int c0 = 0; c0 < nscan; c0 += kIllChunk) {
-        __syncthreads();   // the list of the chunk before has been walked by every wave
-        int sy = 0, sx = 0;
-        float fy = 0.0f, fx = 0.0f;
-        bool keep = false;
-        if (tid < kIllChunk && c0 + tid < nscan) {
-            const size_t p = (size_t)(c0 + tid);
-            const bool vy = illum_split(sc[2 * p], sy, fy), vx = illum_split(sc[2 * p + 1], sx, fx);
-            keep = vy && vx && illum_overlaps(sy, sx, nprb, y0, x0, nz, n);
-        }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) l_cnt[wave] = __popcll(m);
-        __syncthreads();
-        int base = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int c = l_cnt[w];
-            base += w < wave ? c : 0;
-            total += c;
-        }
-        if (keep) {
-            const int at = base + __popcll(m & ((1ull << lane) - 1ull));
-            l_sy[at] = sy; l_sx[at] = sx; l_fy[at] = fy; l_fx[at] = fx;
-        }
+        int at;
+        const int total = illum_stage(sc, nscan, c0, nprb, y0, x0, nz, n, l_sy, l_sx, l_fy, l_fx, l_cnt, at);
         __syncthreads();
         for (int i = 0; i < total; ++i) {
             const int py = __builtin_amdgcn_readfirstlane(l_sy[i]), px = __builtin_amdgcn_readfirstlane(l_sx[i]);

@@ -574,15 +574,23 @@ int ptycho_frc_rings(double* sums, const void* spec, size_t ptheta, size_t s, co
 }
 
 // ---- illumination map and gauge fixing (k_gauge.hpp, libtike.hipfft.gauge): no handle -----------------------------------
-int ptycho_illumination(float* out, const void* scan, const void* probe, size_t ptheta, size_t nscan, int nmodes,
-                        size_t nprb, size_t nz, size_t n, void* stream) {
-    if (!out || !scan || !probe) return fail(PTYCHO_ERR_ARG, "out, scan and probe must not be null");
+// the five sizes of an illumination walk (ptycho_illumination, ptycho_scan_map), the channels (one for the illumination
+// itself) and the modes; flat: the launch also runs one thread per position of every angle (k_scan_keep)
+static int illum_check_sizes(size_t ptheta, size_t nscan, int nval, int nmodes, size_t nprb, size_t nz, size_t n, bool flat) {
     if (ptheta == 0 || nscan == 0 || nprb == 0 || nz == 0 || n == 0) return fail(PTYCHO_ERR_ARG, "all sizes must be positive");
+    if (nval < 1 || nval > kMapMaxVal) return fail(PTYCHO_ERR_ARG, "nval must be in [1, 4]");
     if (nmodes < 1) return fail(PTYCHO_ERR_ARG, "nmodes must be at least 1");
     if (ptheta > kGaugeMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
     if (nz > kGaugeMaxSide || n > kGaugeMaxSide || nprb > kGaugeMaxSide || nscan > 0x7fffffffull ||
-        (nz + kIllTileH - 1) / kIllTileH > 65535)
+        (nz + kIllTileH - 1) / kIllTileH > 65535 || (flat && (ptheta * nscan + 255) / 256 > 0x7fffffffull))
         return fail(PTYCHO_ERR_ARG, "nz, n, nprb or nscan too large for one launch");
+    return PTYCHO_OK;
+}
+
+int ptycho_illumination(float* out, const void* scan, const void* probe, size_t ptheta, size_t nscan, int nmodes,
+                        size_t nprb, size_t nz, size_t n, void* stream) {
+    if (!out || !scan || !probe) return fail(PTYCHO_ERR_ARG, "out, scan and probe must not be null");
+    if (int rc = illum_check_sizes(ptheta, nscan, 1, nmodes, nprb, nz, n, false)) return rc;
     return do_illumination(out, (const float*)scan, (const c32*)probe, (int)ptheta, (int)nscan, nmodes, (int)nprb, (int)nz,
                            (int)n, (hipStream_t)stream);
 }
@@ -739,13 +747,7 @@ int ptycho_scan_map(float* weight, float* out, const float* values, const unsign
     if (!weight || !out || !values || !scan || !probe)
         return fail(PTYCHO_ERR_ARG, "weight, out, values, scan and probe must not be null");
     if (keep && !work) return fail(PTYCHO_ERR_ARG, "work must not be null when keep is given");
-    if (ptheta == 0 || nscan == 0 || nprb == 0 || nz == 0 || n == 0) return fail(PTYCHO_ERR_ARG, "all sizes must be positive");
-    if (nval < 1 || nval > kMapMaxVal) return fail(PTYCHO_ERR_ARG, "nval must be in [1, 4]");
-    if (nmodes < 1) return fail(PTYCHO_ERR_ARG, "nmodes must be at least 1");
-    if (ptheta > kGaugeMaxAngles) return fail(PTYCHO_ERR_ARG, "ptheta must be in [1, 65535]");
-    if (nz > kGaugeMaxSide || n > kGaugeMaxSide || nprb > kGaugeMaxSide || nscan > 0x7fffffffull ||
-        (nz + kIllTileH - 1) / kIllTileH > 65535 || (ptheta * nscan + 255) / 256 > 0x7fffffffull)
-        return fail(PTYCHO_ERR_ARG, "nz, n, nprb or nscan too large for one launch");
+    if (int rc = illum_check_sizes(ptheta, nscan, nval, nmodes, nprb, nz, n, true)) return rc;
     return do_scan_map(weight, out, values, keep, (const float*)scan, (const c32*)probe, (int)ptheta, (int)nscan, nval, nmodes,
                        (int)nprb, (int)nz, (int)n, raw != 0, work, (hipStream_t)stream);
 }

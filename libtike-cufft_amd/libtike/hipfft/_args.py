@@ -1,6 +1,8 @@
-"""Argument checks and pointer idioms that the analysis modules (gauge, fit, prepare, unwrap, frc) share."""
+"""Argument checks, operand placement and pointer idioms that the analysis modules (gauge, fit, prepare, unwrap, frc,
+propagate, resample, dpc) share."""
 import numbers
 
+import numpy as np
 import torch
 
 from .operators import _ptr
@@ -64,3 +66,24 @@ def _device_of(x, module):
     if not torch.cuda.is_available():
         raise RuntimeError("libtike.hipfft.%s needs a ROCm GPU; there is no CPU path" % module)
     return torch.device("cuda", torch.cuda.current_device())
+
+
+def _to_device(arrays, module, message):
+    """The operands (device tensors or NumPy arrays, which are copied; ``None`` passes through) as contiguous tensors on
+    one device, and that device: the tensors' own, or the current one if there is none.  A host tensor raises
+    ``ValueError(message)``; ``module`` names the caller where there is no GPU."""
+    dev = None
+    for t in arrays:
+        if isinstance(t, torch.Tensor):
+            if not t.is_cuda:
+                raise ValueError(message)
+            if dev is not None and t.device != dev:
+                raise ValueError("operands live on different devices: %s and %s" % (dev, t.device))
+            dev = t.device
+    if dev is None:
+        dev = _device_of(None, module)
+    with torch.cuda.device(dev):
+        moved = [None if t is None else
+                 (t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t)).to(dev)).contiguous()
+                 for t in arrays]
+    return moved, dev

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from ._args import _array, _check_out, _device_of, _dtype, _need_array, _opt, _size
+from ._args import _array, _check_out, _dtype, _need_array, _opt, _size, _to_device
 from .gauge import check_illumination
 from .operators import _ptr, _stream
 from .unwrap import check_unwrap
@@ -110,24 +110,7 @@ def check_first_look(data, scan, probe, nz, n, mask=None, reference="mean", keep
     return ptheta, nscan, ndet, int(nz), int(n), ref
 
 
-def _to_device(*arrays):
-    """Device tensors of the operands (NumPy arrays are copied, ``None`` passes through) on one device; that device."""
-    dev = None
-    for t in arrays:
-        if isinstance(t, torch.Tensor):
-            if not t.is_cuda:
-                raise ValueError("operands must be device tensors or NumPy arrays")
-            if dev is not None and t.device != dev:
-                raise ValueError("operands live on different devices: %s and %s" % (dev, t.device))
-            dev = t.device
-    if dev is None:
-        dev = _device_of(None, "dpc")
-    out = []
-    for t in arrays:
-        if t is not None and not isinstance(t, torch.Tensor):
-            t = torch.from_numpy(np.ascontiguousarray(t)).to(dev)
-        out.append(None if t is None else t.contiguous())
-    return out, dev
+_HOST = "operands must be device tensors or NumPy arrays"   # what a host tensor among the operands raises
 
 
 # ---- the pieces ---------------------------------------------------------------------------------------------------------------
@@ -149,7 +132,7 @@ def frame_moments(data, mask=None, darkfield=None):
     ptheta, nscan, ndet, radius = check_frame_moments(data, mask, darkfield)
     if mask is not None and not isinstance(mask, torch.Tensor):
         mask = np.ascontiguousarray(np.asarray(mask) != 0)
-    (d, m), dev = _to_device(data, mask)
+    (d, m), dev = _to_device((data, mask), "dpc", _HOST)
     if m is not None:
         m = (m != 0).to(torch.uint8).contiguous()
     words = int(nat.frame_moments_work_words(ptheta, nscan, ndet))
@@ -181,7 +164,7 @@ def scan_map(values, scan, probe, nz, n, keep=None, normalize=True):
         raise TypeError("normalize must be a bool, got %r" % (normalize,))
     if keep is not None and not isinstance(keep, torch.Tensor):
         keep = np.ascontiguousarray(np.asarray(keep) != 0)
-    (v, s, p, k), dev = _to_device(values, scan, probe, keep)
+    (v, s, p, k), dev = _to_device((values, scan, probe, keep), "dpc", _HOST)
     v3 = v.reshape(ptheta, nscan, nval)
     if k is not None:
         k = (k != 0).to(torch.uint8).contiguous()
@@ -214,7 +197,7 @@ def integrate_gradient(gy, gx, weight=None, tol=1e-4, maxiter=None, check_every=
     ``"converged"`` and ``"status"``.  For 2-D input the angle axis is dropped.  Bitwise reproducible.
     """
     ptheta, nz, n, maxiter = check_integrate(gy, gx, weight, tol, maxiter, check_every, out)
-    (y, x, w), dev = _to_device(gy, gx, weight)
+    (y, x, w), dev = _to_device((gy, gx, weight), "dpc", _HOST)
     if w is not None:
         w = w.to(torch.float32).contiguous()
     _check_out(out, dev, "out must be a contiguous tensor on the operands' device")
@@ -277,7 +260,7 @@ def first_look(data, scan, probe, nz, n, mask=None, reference="mean", keep=None,
                                                        tol, maxiter)
     if keep is not None and not isinstance(keep, torch.Tensor):
         keep = np.ascontiguousarray(np.asarray(keep) != 0)
-    (d, s, p, k), dev = _to_device(data, scan, probe, keep)
+    (d, s, p, k), dev = _to_device((data, scan, probe, keep), "dpc", _HOST)
     with torch.cuda.device(dev):
         fm = frame_moments(d, mask, darkfield)
         mom = fm["moments"]

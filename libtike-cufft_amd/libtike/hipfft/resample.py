@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from ._args import _check_out, _device_of, _dtype, _need_array, _opt
+from ._args import _check_out, _dtype, _need_array, _opt, _to_device
 from .operators import _ptr, _stream
 
 __all__ = ["spline_prefilter", "warp", "rotate", "zoom", "shift", "center_of_mass", "check_warp"]
@@ -108,23 +108,7 @@ def check_warp(x, matrix=None, offset=None, shape=None, order=3, mode="constant"
     return lead, ny, nx, int(oh), int(ow), cplx, xf
 
 
-def _to_device(x, *others):
-    """``x`` and the other arrays (``None`` passes) as contiguous tensors on one device; that device."""
-    dev = None
-    for t in (x,) + others:
-        if isinstance(t, torch.Tensor):
-            if not t.is_cuda:
-                raise ValueError("x and weight must be device tensors or NumPy arrays")
-            if dev is not None and t.device != dev:
-                raise ValueError("operands live on different devices: %s and %s" % (dev, t.device))
-            dev = t.device
-    if dev is None:
-        dev = _device_of(None, "resample")
-    with torch.cuda.device(dev):
-        moved = [None if t is None else
-                 (t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t))).to(dev).contiguous()
-                 for t in (x,) + others]
-    return moved, dev
+_HOST = "x and weight must be device tensors or NumPy arrays"   # what a host tensor among the operands raises
 
 
 def _prefilter(xi, nimg, ny, nx, cplx, order, res):
@@ -145,7 +129,7 @@ def spline_prefilter(x, order=3, out=None):
         _need_array(out, "out")
         if _dtype(out) != _dtype(x) or tuple(out.shape) != tuple(x.shape):
             raise ValueError("out must be %s of shape %s" % (_dtype(x), tuple(x.shape)))
-    (xi,), dev = _to_device(x)
+    (xi,), dev = _to_device((x,), "resample", _HOST)
     _check_out(out, dev, "out must be a contiguous tensor on the operands' device")
     with torch.cuda.device(dev):
         res = torch.empty_like(xi) if out is None else out
@@ -157,7 +141,7 @@ def _warp(x, matrix, offset, shape, order, mode, cval, prefilter, out, force_glo
     the int32 ``[..., tiles_y, tiles_x]`` map of the path each output tile took (0 outside, 1 LDS, 2 global)."""
     lead, ny, nx, oh, ow, cplx, xf = check_warp(x, matrix, offset, shape, order, mode, cval, prefilter, out)
     nimg = xf.shape[0]
-    (xi,), dev = _to_device(x)
+    (xi,), dev = _to_device((x,), "resample", _HOST)
     _check_out(out, dev, "out must be a contiguous tensor on the operands' device")
     with torch.cuda.device(dev):
         coef = xi
@@ -266,7 +250,7 @@ def center_of_mass(x, weight=None, which="value"):
             raise TypeError("weight must be float32, got %s" % _dtype(weight))
         if tuple(weight.shape) != tuple(x.shape):
             raise ValueError("weight must have x's shape %s, got %s" % (tuple(x.shape), tuple(weight.shape)))
-    (xi, w), dev = _to_device(x, weight)
+    (xi, w), dev = _to_device((x, weight), "resample", _HOST)
     with torch.cuda.device(dev):
         work = torch.empty((int(nat.moments_work_words(nimg, ny, nx)),), dtype=torch.float64, device=dev)
         sums = torch.empty(lead + (5,), dtype=torch.float64, device=dev)

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from ._args import _check_out, _device_of, _dtype, _need_array, _opt
+from ._args import _check_out, _dtype, _need_array, _opt, _to_device
 from .operators import _ptr, _stream
 
 __all__ = ["unwrap_phase", "phase_residues", "check_unwrap"]
@@ -65,27 +65,14 @@ def check_unwrap(x, weight=None, congruent=True, tol=1e-4, maxiter=None, check_e
 
 def _on_device(x, weight):
     """``x`` as contiguous float32 phase and ``weight`` as contiguous float32 (or ``None``) on one device; that device."""
-    dev = None
-    for t in (x, weight):
-        if isinstance(t, torch.Tensor):
-            if not t.is_cuda:
-                raise ValueError("x and weight must be device tensors or NumPy arrays")
-            if dev is not None and t.device != dev:
-                raise ValueError("operands live on different devices: %s and %s" % (dev, t.device))
-            dev = t.device
-    if dev is None:
-        dev = _device_of(None, "unwrap")
-
-    def move(t):
-        return (t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t))).to(dev)
+    (xd, weight), dev = _to_device((x, weight), "unwrap", "x and weight must be device tensors or NumPy arrays")
     with torch.cuda.device(dev):
-        x = move(x)
-        phase = torch.angle(x) if x.is_complex() else x
+        phase = torch.angle(xd) if xd.is_complex() else xd
         phase = phase.to(torch.float32).contiguous()
-        if phase.data_ptr() == x.data_ptr():
+        if isinstance(x, torch.Tensor) and phase.data_ptr() == x.data_ptr():
             phase = phase.clone()                      # never alias the caller's array: out= may be x itself
         if weight is not None:
-            weight = move(weight).to(torch.float32).contiguous()
+            weight = weight.to(torch.float32).contiguous()
     return phase, weight, dev
 
 

@@ -3,18 +3,11 @@
 functions the kernel uses, fills an emulated ring lane-linearly as the hardware does and reads it back as the threads
 do: every tile element requested once from a 16-byte-aligned source, inside its own wave's segment, and every thread's
 16 reads the rows ``Fft::load`` names for it.  No GPU involved."""
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "libtike-cufft_amd", "csrc")
+import host_build
 
 
 def test_adjreg_tile_ring_on_host(tmp_path):
-    exe = str(tmp_path / "pty_host_adjdma")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2", "-Wall", "-Werror",
-                    os.path.join(CSRC, "host_adjdma.cpp"), "-o", exe], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.build("host_adjdma", tmp_path)(check=False)
     assert out.returncode == 0, out.stdout
     lines = out.stdout.splitlines()
     assert lines[-1] == "OK", out.stdout

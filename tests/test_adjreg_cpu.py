@@ -2,18 +2,11 @@
 ``csrc/host_adjreg.cpp`` emulates the threads of one workgroup of ``k_cols_adjreg`` with the very arithmetic the kernel
 uses -- ownership, retire, clamped tile rows, combine -- for ndet = 256 and 512, and compares every object pixel with a
 four-tap scatter in float64.  No GPU involved."""
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "libtike-cufft_amd", "csrc")
+import host_build
 
 
 def test_adjreg_window_on_host(tmp_path):
-    exe = str(tmp_path / "pty_host_adjreg")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2",
-                    os.path.join(CSRC, "host_adjreg.cpp"), "-o", exe], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.build("host_adjreg", tmp_path)(check=False)
     assert out.returncode == 0, out.stdout
     lines = out.stdout.splitlines()
     assert lines[-1] == "OK", out.stdout

@@ -4,18 +4,11 @@ allows split" x mode against the table of the ladders the launch sites used to w
 only implied: split only at 256 and only with the window, the register window only at 256 / 512 and only for the object
 adjoint, no windowed kernel where the window does not fit, 32-column strips only for the split forward pass.  The in-library
 profiler cannot tell a windowed kernel from a plain one; this sweep can.  No GPU involved."""
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "libtike-cufft_amd", "csrc")
+import host_build
 
 
 def test_column_path_rule_on_host(tmp_path):
-    exe = str(tmp_path / "pty_host_colpath")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2", "-Wall", "-Werror",
-                    os.path.join(CSRC, "host_colpath.cpp"), "-o", exe], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.build("host_colpath", tmp_path)(check=False)
     assert out.returncode == 0, out.stdout
     lines = out.stdout.splitlines()
     assert lines[-1] == "OK", out.stdout

@@ -10,13 +10,13 @@ of the raster and with it these figures in the third digit.
 import ctypes
 import inspect
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_build  # noqa: E402
 import dpc_ref as ref  # noqa: E402
 import gauge_ref  # noqa: E402
 
@@ -39,14 +39,8 @@ def nat():
 # ---- the index logic of csrc/k_dpc.hpp, built for the host --------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("dpc") / "pty_host_dpc")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2", "-Wall", "-Werror",
-                    os.path.join(CSRC, "host_dpc.cpp"), "-o", exe], check=True)
-
-    def run(*args, stdin=None):
-        out = subprocess.run([exe] + [str(a) for a in args], input=stdin, capture_output=True, text=True, check=True)
-        return out.stdout
-    return run
+    program = host_build.build("host_dpc", tmp_path_factory.mktemp("dpc"))
+    return lambda *args, stdin=None: program(*args, stdin=stdin).stdout
 
 
 def test_host_sweep_is_clean(host):

@@ -4,17 +4,16 @@ of ``libtike.hipfft.fit``.  No GPU needed."""
 import ctypes
 import inspect
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_build  # noqa: E402
 import fit_ref as ref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "libtike-cufft_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -81,14 +80,8 @@ def test_unmeasured_pixels_may_hold_anything_in_the_restatement():
 # ---- the partition of csrc/k_fit.hpp, built for the host ------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_walk(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("fit") / "pty_host_fit")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2",
-                    os.path.join(CSRC, "host_fit.cpp"), "-o", exe], check=True)
-
-    def walk(ptheta, nscan, npix):
-        out = subprocess.run([exe, str(ptheta), str(nscan), str(npix)], capture_output=True, text=True, check=True)
-        return [int(v) for v in out.stdout.split()]
-    return walk
+    program = host_build.build("host_fit", tmp_path_factory.mktemp("fit"))
+    return lambda ptheta, nscan, npix: [int(v) for v in program(ptheta, nscan, npix).stdout.split()]
 
 
 WALK_SHAPES = [(pt_, ns, nd * nd) for pt_, ns, nd, _ in ref.CASES.values()] + [

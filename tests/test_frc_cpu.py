@@ -5,17 +5,16 @@ C ABI and of ``frc``.  No GPU needed."""
 import ctypes
 import inspect
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_build  # noqa: E402
 import frc_ref as ref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "libtike-cufft_amd", "csrc")
 SIDES = list(range(16, 1025)) + [2048]
 
 
@@ -127,10 +126,7 @@ def test_default_side(lib):
 
 # ---- the ring enumeration of csrc/k_frc.hpp, built for the host ---------------------------------------------------------
 def test_host_ring_enumeration_covers_every_pixel_once(tmp_path):
-    exe = str(tmp_path / "pty_host_frc")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2",
-                    os.path.join(CSRC, "host_frc.cpp"), "-o", exe], check=True)
-    out = subprocess.run([exe], input=" ".join(map(str, SIDES)) + "\n", capture_output=True, text=True, check=True)
+    out = host_build.build("host_frc", tmp_path)(stdin=" ".join(map(str, SIDES)) + "\n")
     lines = out.stdout.split("\n")[:-1]
     assert len(lines) == len(SIDES)
     ring_of_r2 = np.rint(np.sqrt(np.arange(2 * 1024 ** 2 + 1))).astype(np.int64)

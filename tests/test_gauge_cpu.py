@@ -5,18 +5,17 @@ the kernel walks it, and the argument checks of the C ABI and of ``libtike.hipff
 import ctypes
 import inspect
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_build  # noqa: E402
 import gauge_ref as ref  # noqa: E402
 import recon_metrics as rm  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "libtike-cufft_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -114,15 +113,12 @@ def test_object_and_probe_companion_keep_whole_pixel_exit_waves():
 # ---- the index logic of csrc/k_gauge.hpp, built for the host --------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_walk(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("gauge") / "pty_host_gauge")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2",
-                    os.path.join(CSRC, "host_gauge.cpp"), "-o", exe], check=True)
+    program = host_build.build("host_gauge", tmp_path_factory.mktemp("gauge"))
 
     def walk(scan, nprb, nz, n):
         text = "%d %d %d %d %d\n%s\n" % (scan.shape[0], scan.shape[1], nprb, nz, n,
                                          " ".join(str(int(v)) for v in scan.view(np.uint32).ravel()))
-        out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True)
-        return [int(v) for v in out.stdout.split()]
+        return [int(v) for v in program(stdin=text).stdout.split()]
     return walk
 
 

@@ -8,8 +8,9 @@ import subprocess
 
 import pytest
 
+import host_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "libtike-cufft_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -112,10 +113,7 @@ def test_zoom_kernel_eligibility(nat):
 def test_fft_core_on_host(tmp_path):
     """Stockham index math of csrc/fft_core.hpp for every plan (16..2048, both
     directions) emulated thread by thread on the host against a naive DFT."""
-    exe = str(tmp_path / "pty_host_check")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2",
-                    os.path.join(CSRC, "host_check.cpp"), "-o", exe], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.build("host_check", tmp_path)(check=False)
     assert out.returncode == 0, out.stdout
     assert "OK" in out.stdout.splitlines()[-1]
 
@@ -125,10 +123,7 @@ def test_run_split_on_host(tmp_path):
     strips, 1 .. 304 CUs and the launchers' workgroup targets: every run fits RunMeta (<= kRunMax positions, the only
     guard of load_run), the runs cover the positions, none is empty, and the result is the formula the four launch
     sites used to write out."""
-    exe = str(tmp_path / "pty_host_runsplit")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2", "-Wall",
-                    os.path.join(CSRC, "host_runsplit.cpp"), "-o", exe], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.build("host_runsplit", tmp_path)(check=False)
     assert out.returncode == 0, out.stdout
     assert out.stdout.splitlines()[-1] == "host_runsplit: 360000 cases, longest run 128 of 128, 0 errors", out.stdout
 

@@ -3,7 +3,6 @@ defining properties, the Jacobi solve of csrc/k_modes.hpp built with the host co
 the C ABI's argument checks.  No GPU needed."""
 import ctypes
 import os
-import subprocess
 import sys
 import warnings
 
@@ -15,11 +14,11 @@ from oracle import cg_oracle as cg
 from oracle import ptycho_oracle as op
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_build  # noqa: E402
 import ortho_modes as om  # noqa: E402
 from cg_reference import ReferenceSolver  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "libtike-cufft_amd", "csrc")
 
 
 mixed_probe = om.mixed_probe
@@ -90,17 +89,14 @@ def test_reference_rotates_companions_by_the_same_v():
 # ---- the host build of k_modes.hpp's Jacobi solve ----------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_jacobi(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("jacobi") / "host_jacobi")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2", "-Wall", "-Werror",
-                    os.path.join(CSRC, "host_jacobi.cpp"), "-o", exe], check=True)
+    program = host_build.build("host_jacobi", tmp_path_factory.mktemp("jacobi"))
 
     def solve(mats):
         text = []
         for g in mats:
             text.append(str(g.shape[0]))
             text.extend("%.17g %.17g" % (z.real, z.imag) for z in g.ravel())
-        out = subprocess.run([exe], input="\n".join(text) + "\n", capture_output=True, text=True, check=True)
-        words = out.stdout.split()
+        words = program(stdin="\n".join(text) + "\n").stdout.split()
         res, pos = [], 0
         for g in mats:
             m = g.shape[0]

@@ -4,13 +4,13 @@ the argument checks of the C ABI and of ``libtike.hipfft.prepare``.  No GPU need
 import ctypes
 import inspect
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_build  # noqa: E402
 import prepare_ref as ref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -139,14 +139,8 @@ def test_the_cases_exercise_what_they_are_named_for():
 # ---- the partition and the index map of csrc/k_prepare.hpp, built for the host ---------------------------------------------
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("prepare") / "pty_host_prepare")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2", "-Wall", "-Werror",
-                    os.path.join(CSRC, "host_prepare.cpp"), "-o", exe], check=True)
-
-    def run(*args):
-        out = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, check=True)
-        return out.stdout
-    return run
+    program = host_build.build("host_prepare", tmp_path_factory.mktemp("prepare"))
+    return lambda *args: program(*args).stdout
 
 
 WALK_SHAPES = list(ref.CASES.values()) + [(1, 4096, 256), (1, 1, 1), (3, 5, 2), (1, 129, 3), (2, 1000, 33), (1, 257, 45),

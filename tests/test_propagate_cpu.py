@@ -2,17 +2,16 @@
 NumPy restatement (tests/propagate_ref.py) against the analytic Gaussian beam, its focus search, and the host program
 that walks the plain C++ of csrc/k_propagate.hpp.  No GPU."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_build  # noqa: E402
 import propagate_ref as ref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "libtike-cufft_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -170,8 +169,5 @@ def test_reference_focus():
 
 
 def test_host_program(tmp_path):
-    exe = str(tmp_path / "pty_host_propagate")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2", "-Wall", "-Werror",
-                    os.path.join(CSRC, "host_propagate.cpp"), "-o", exe], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
+    out = host_build.build("host_propagate", tmp_path)().stdout
     assert out.startswith("host_propagate:") and out.strip().endswith(" 0 errors"), out

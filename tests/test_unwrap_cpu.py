@@ -5,13 +5,13 @@ and of ``libtike.hipfft.unwrap``.  No GPU needed."""
 import ctypes
 import inspect
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_build  # noqa: E402
 import unwrap_ref as ref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -192,14 +192,8 @@ def test_weights_that_are_not_positive_and_finite_count_as_zero():
 # ---- the tile / halo index logic of csrc/k_unwrap.hpp, built for the host ---------------------------------------------------
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("unwrap") / "pty_host_unwrap")
-    subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O2", "-Wall", "-Werror",
-                    os.path.join(CSRC, "host_unwrap.cpp"), "-o", exe], check=True)
-
-    def run(*args):
-        out = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, check=True)
-        return out.stdout
-    return run
+    program = host_build.build("host_unwrap", tmp_path_factory.mktemp("unwrap"))
+    return lambda *args: program(*args).stdout
 
 
 def test_host_walk_owns_every_pixel_once_and_visits_every_edge_from_both_ends(host, nat):
