@@ -112,7 +112,10 @@ int launch_rows_split(ptycho_handle h, RowArgs a, hipStream_t st) {
     if (a.nrows <= 0) return PTYCHO_OK;
     const long long nitems = (a.nrows / N) * 16;
     // measured at 4096 x 256^2: forward best with ~32 workgroups per CU in the grid (0.73 ms vs 0.75
-    // at 8), adjoint best with one item per workgroup (0.70 ms vs 0.78); PTYCHO_HIP_ROWGRID overrides
+    // at 8), adjoint best with one item per workgroup (0.70 ms vs 0.78); PTYCHO_HIP_ROWGRID overrides.  Swept again with the
+    // forward pass's 16 requests per item in one batch (profiles/r19/rows_split_issue.txt): forward 0.744 / 0.719 / 0.700 /
+    // 0.713 / 0.702 ms at 8 / 16 / 32 / 64 / 128; adjoint 0.775 / 0.757 / 0.717 / 0.702 ms at 8 / 16 / 64 / 128 against
+    // 0.707 - 0.722 at 256, one spread of its runs and so not adopted.  Both values stay.
     static const int env_mult = exp_env("PTYCHO_HIP_ROWGRID", 0);
     const int mult = env_mult > 0 ? env_mult : (DIR < 0 ? 32 : 256);
     long long grid = nitems < (long long)h->n_cu * mult ? nitems : (long long)h->n_cu * mult;

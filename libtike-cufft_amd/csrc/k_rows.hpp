@@ -92,6 +92,18 @@ __global__ __launch_bounds__(256) void k_rows(const RowArgs a) {
     }
 }
 
+// An unconditional global load whose value is masked afterwards (m = all ones or zero, made opaque by the caller so that the
+// AND does not turn back into a select).  `pred ? load(p) : zero` puts every request into a branch of its own
+// (s_and_saveexec / s_cbranch_execz), and the branches pin each request behind the previous one's wait: the fused row
+// stages showed 50-100 branches and at most 2-4 requests in flight per thread.
+__device__ __forceinline__ c32 load_masked(const c32* __restrict__ p, unsigned m) {
+    const c32 val = __builtin_nontemporal_load(p);
+    return c32{__uint_as_float(__float_as_uint(val.x) & m), __uint_as_float(__float_as_uint(val.y) & m)};
+}
+__device__ __forceinline__ float load_masked(const float* __restrict__ p, unsigned m) {
+    return __uint_as_float(__float_as_uint(__builtin_nontemporal_load(p)) & m);
+}
+
 // ---------------------------------------------------------------------------
 // Split variant for N = 256 (= 16 x 16): the column kernels do only ONE radix-16 step of
 // the DFT over y (thread local, no exchange, no barrier); the other radix-16 step runs
@@ -122,7 +134,6 @@ __global__ __launch_bounds__(256) void k_rows_split(const RowArgs a) {
     fft.init(j0, a.table);
     auto put = [&](int i, c32 val) { lds[L::at(f, i)] = val; };   // the LDS row of this thread's transform
     auto get = [&](int i) { return lds[L::at(f, i)]; };
-    const c32 zero = c32{0.0f, 0.0f};
     const long long nitems = (a.nrows / N) * 16;
     for (long long item = blockIdx.x; item < nitems; item += gridDim.x) {
         const long long tile = item / 16;
@@ -134,14 +145,31 @@ __global__ __launch_bounds__(256) void k_rows_split(const RowArgs a) {
         if (DIR < 0) {
             // ---- second radix-16 step of the DFT over y, thread = column x ------------------
             const int x = tid;
-            const bool colok = x >= a.xa && x < a.xb;
+            // All 16 rows are requested back to back and the column limits applied afterwards (load_masked).  With
+            // `colok ? load : zero` on 64-bit lane addresses the requests went out 3, 4, 4, 2, 2, 1 at a time, each group
+            // behind the previous one's wait: five dependent HBM round trips per item.  Address = row base in scalar
+            // registers + one 32-bit lane offset (saddr form).  Base and offset are opaque to the compiler: it otherwise
+            // adds the lane part to the tile base first (loop invariant across the rows) and is back at a 64-bit
+            // add per request.
+            unsigned xbytes = (unsigned)x * (unsigned)sizeof(c32), colm = (x >= a.xa && x < a.xb) ? 0xffffffffu : 0u;
+            asm volatile("" : "+v"(xbytes), "+v"(colm));
+            // the item's 15 inter-step twiddles, one per lane (t = lane % 16), requested ahead of the rows and broadcast at
+            // the multiply, as the inverse branch does: read at the uniform index they were 15 vector loads in the middle
+            // of the rows' queue
+            const c32 wl = a.table[(jp * (tid & 15)) & (N - 1)];
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
-                const c32 val = __builtin_nontemporal_load(sbase + (size_t)(jp + 16 * t) * N + x);
-                v[t] = colok ? val : zero;
+                typedef const __attribute__((address_space(1))) char* gbytes;
+                gbytes row = (gbytes)(sbase + (size_t)(jp + 16 * t) * N);
+                asm("" : "+s"(row));
+                v[t] = load_masked((const c32*)(row + xbytes), colm);
             }
 #pragma unroll
-            for (int t = 1; t < 16; ++t) v[t] = cmul(v[t], a.table[(jp * t) & (N - 1)]);   // uniform index
+            for (int t = 1; t < 16; ++t) {
+                const c32 w = c32{__int_as_float(__builtin_amdgcn_readlane(__float_as_int(wl.x), t)),
+                                  __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wl.y), t))};
+                v[t] = cmul(v[t], w);   // the same two fused multiply-adds as with the factor in vector registers: same bits
+            }
             fft_reg<16, -1>(v);
 #pragma unroll
             for (int t = 0; t < 16; ++t) lds[L::at(t, x)] = v[brev(t, 4)];
@@ -253,18 +281,6 @@ struct TrialTerm {
         }
     }
 };
-
-// An unconditional global load whose value is masked afterwards (m = all ones or zero, made opaque by the caller so that the
-// AND does not turn back into a select).  `pred ? load(p) : zero` puts every request into a branch of its own
-// (s_and_saveexec / s_cbranch_execz), and the branches pin each request behind the previous one's wait: the fused row
-// stages showed 50-100 branches and at most 2-4 requests in flight per thread.
-__device__ __forceinline__ c32 load_masked(const c32* __restrict__ p, unsigned m) {
-    const c32 val = __builtin_nontemporal_load(p);
-    return c32{__uint_as_float(__float_as_uint(val.x) & m), __uint_as_float(__float_as_uint(val.y) & m)};
-}
-__device__ __forceinline__ float load_masked(const float* __restrict__ p, unsigned m) {
-    return __uint_as_float(__float_as_uint(__builtin_nontemporal_load(p)) & m);
-}
 
 enum RowEp { EP_STATS = 1, EP_PROJECT = 2, EP_LINESEARCH = 3, EP_CROSS = 6, EP_LINESEARCH_M = 7, EP_STATS_M = 8 };
 constexpr int kMaxModes = 8;   // EP_LINESEARCH_M: slot pairs (2k, 2k+1), k < nmodes
