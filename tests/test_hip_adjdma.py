@@ -1,6 +1,6 @@
 """Split adjoints at ndet = 256 after the inter-step twiddle moved into the row pass and the object adjoint's tiles stream
 through an LDS ring filled by LDS-DMA (``k_rows_split<256, +1>``, ``k_cols_adjreg<256, split>``, the split probe adjoint
-of ``k_cols_gatherwin``), against the CPU oracle in double at ``REL_MAX`` of ``tests/test_hip_operators.py``.
+of ``k_cols_gatherwin``), against the CPU oracle in double at ``REL_MAX`` of ``tests/hip_common.py``.
 
 The edges are those of the ring: a skipped position requests nothing and waits for nothing (first, last and two
 consecutive middle positions of a run); runs of one and of three positions; a launch that starts at ``k_begin`` != 0
@@ -14,28 +14,14 @@ import numpy as np
 import pytest
 
 from oracle import ptycho_oracle as op
+from hip_common import REL_MAX, host, pt, rel_max  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-REL_MAX = 2e-5
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
 
 
 def dev(x):
     import torch
     return torch.as_tensor(np.array(x), device="cuda")   # a copy: the shared case arrays are read-only
-
-
-def host(x):
-    return x.detach().cpu().numpy()
 
 
 def scan_of(name):
@@ -106,10 +92,6 @@ def probe_case(name):
     psi.setflags(write=False)
     want.setflags(write=False)
     return psi, want
-
-
-def rel_max(got, want):
-    return np.abs(got.astype(np.complex128) - want).max() / np.abs(want).max()
 
 
 def solver(pt, c):

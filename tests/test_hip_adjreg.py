@@ -11,29 +11,16 @@ import numpy as np
 import pytest
 
 from oracle import ptycho_oracle as op
+from hip_common import REL_MAX, host, pt, rel_max  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-REL_MAX = 2e-5
 GAPS = (0, 1, 23, 24, 25, 47, 48, 287, 288, 289, 600)   # around RPG = 24, 2 RPG and the window height 288
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
 
 
 def dev(x):
     import torch
     return torch.as_tensor(np.array(x), device="cuda")   # a copy: the shared case arrays are read-only
-
-
-def host(x):
-    return x.detach().cpu().numpy()
 
 
 def scan_of(name):
@@ -87,10 +74,6 @@ def case(name):
     for a in (scan, probe, y, want):
         a.setflags(write=False)
     return dict(ndet=ndet, nprb=nprb, ntheta=ntheta, nz=nz, n=n, nscan=nscan, scan=scan, probe=probe, y=y, want=want)
-
-
-def rel_max(got, want):
-    return np.abs(got.astype(np.complex128) - want).max() / np.abs(want).max()
 
 
 def check_adj(pt, name, split=True):

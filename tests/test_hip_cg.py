@@ -3,34 +3,17 @@ import numpy as np
 import pytest
 
 from oracle import cg_oracle as cg
+from cg_harness import problem
+from hip_common import dev, pt  # noqa: F401
 from libtike.hipfft import synthetic as syn
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
-
-
 def setup(nmodes=1, ndet=32, seed=7):
-    p = syn.make_problem(6, 6, 6, ndet, ndet, seed=seed)
-    probe = syn.hermite_modes(ndet, nmodes) if nmodes > 1 else p["probe"][:, None].copy()
-    # A smooth Gaussian probe on a flat start object predicts ~zero amplitude on most of the
-    # detector, where the projection f/|f| takes the phase of float32 rounding noise: the CG
-    # trajectory is then not reproducible across FFT implementations (the reference's cuFFT
-    # included).  A random phase screen spreads the model over the whole detector.
-    rng = np.random.default_rng(seed + 100)
-    probe = probe * np.exp(2j * np.pi * rng.random(probe.shape[-2:]))
-    ora = cg.OracleSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
-    data = np.zeros((1, p["nscan"], ndet, ndet), np.float32)
-    for k in range(probe.shape[1]):
-        data += np.abs(ora.fwd(p["psi"], p["scan"], probe[:, k])) ** 2
-    return p, probe.astype(np.complex64), ora, data
+    """cg_harness.problem (phase-screened probe(s), consistent data) and the oracle on its geometry."""
+    p, probe, data = problem(ndet, nmodes, seed)
+    return p, probe, cg.OracleSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"]), data
 
 
 @pytest.mark.parametrize("nmodes,recover", [(1, False), (1, True), (2, True)])
@@ -379,32 +362,29 @@ def test_work_slots_follow_the_shared_gathers(pt):
     does not depend on it, and a released slot is allocated again on demand."""
     import torch
     p, probe, ora, data = setup(1)
-    D = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
     res = {}
     with pt.CGPtychoSolver(p["nscan"], 32, 32, 1, p["nz"], p["n"]) as slv:
         slv.verbose = False
         for share in (True, False, True):
             slv.share_ones = share
-            out = slv.run(D(data), torch.ones_like(D(p["psi"])), D(p["scan"]).clone(), D(probe).clone(), piter=4)
+            out = slv.run(dev(data), torch.ones_like(dev(p["psi"])), dev(p["scan"]).clone(), dev(probe).clone(), piter=4)
             slots = slv.work_slots_allocated()
             assert slots == ([0, 1, 2, 3] if share else [0, 1]), (share, slots)
             res.setdefault(share, []).append(out["psi"].cpu().numpy())
         slv.release_work(3)
         assert slv.work_slots_allocated() == [0, 1, 2]
-        again = slv.run(D(data), torch.ones_like(D(p["psi"])), D(p["scan"]).clone(), D(probe).clone(), piter=4)["psi"].cpu().numpy()
+        again = slv.run(dev(data), torch.ones_like(dev(p["psi"])), dev(p["scan"]).clone(), dev(probe).clone(), piter=4)["psi"].cpu().numpy()
     assert np.array_equal(res[True][0], res[True][1]) and np.array_equal(res[True][0], again)
     assert np.abs(res[True][0] - res[False][0]).max() <= 1e-5 * np.abs(res[True][0]).max()
 
 
 def test_profile_read_accepts_the_16_entry_arrays_of_earlier_headers(pt):
     import ctypes
-    import torch
     from libtike.hipfft import _native as nat
     p, probe, ora, data = setup(1)
-    D = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
     GUARD = -7777
     with pt.PtychoCuFFT(p["nscan"], 32, 32, 1, p["nz"], p["n"]) as slv:
-        psi, scan, prb = D(p["psi"]), D(p["scan"]), D(probe[:, 0])
+        psi, scan, prb = dev(p["psi"]), dev(p["scan"]), dev(probe[:, 0])
 
         def read(n, size):
             # arrays of `size` entries, the ones past n filled with guard words; n tells the library how many it may write
@@ -439,14 +419,13 @@ def test_pending_deferred_gradient_is_guarded(pt):
     from libtike.hipfft import _native as nat
     from libtike.hipfft.ptycho import _ptr, _stream
     p, probe, ora, data = setup(1)
-    D = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
     with pt.CGPtychoSolver(p["nscan"], 32, 32, 1, p["nz"], p["n"]) as slv:
         h = slv._h
         nat.check(nat.set_option(h, b"deterministic", 1))
         nat.check(nat.set_option(h, b"defer_finish", 1))
         st = torch.zeros(nat.ST_WORDS, dtype=torch.float64, device="cuda")
         st[nat.ST_HINT:nat.ST_HINT + 2] = 14.0
-        psi, scan, prb, dat = torch.ones_like(D(p["psi"])), D(p["scan"]), D(probe[:, 0]).contiguous(), D(data)
+        psi, scan, prb, dat = torch.ones_like(dev(p["psi"])), dev(p["scan"]), dev(probe[:, 0]).contiguous(), dev(data)
         grad, grad0, dpsi = torch.empty_like(psi), torch.zeros_like(psi), torch.zeros_like(psi)
         S = _stream()
         nat.check(nat.cg_obj_begin(h, _ptr(st), _ptr(psi), _ptr(scan), _ptr(prb), _ptr(dat), S))

@@ -25,12 +25,11 @@ from oracle import ptycho_oracle as op
 from libtike.hipfft import synthetic as syn
 
 import cg_stages as cs
+from hip_common import FACTOR, REL_MAX, crand, dev, host
 
 pytestmark = pytest.mark.gpu
 
-REL_MAX = 2e-5     # elementwise, relative to the largest element (the operator bound of test_hip_operators.py)
 SUM_REL = 2e-6     # sums, relative to the sum of the magnitudes of their terms
-FACTOR = 4         # the device against the float32 reference's own error
 
 # Detector columns per strip, ColCfg<N>::C of csrc/ptycho_common.hpp (T = N / E of the Stockham plan, fft_core.hpp).  A fused
 # row stage runs its full-width variant (FW = true: unpredicated loads) when the strips of the probe, strip_range(), cover the
@@ -68,10 +67,6 @@ def gid(g):
     return "n%d-p%d-%s-s%d-t%d" % (g[0], g[1], "full" if full_width(g[0], g[1]) else "pred", g[2] * g[3], g[5])
 
 
-def crand(rng, shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
-
-
 def make_problem(ndet, nprb, ny, nx, step, ptheta, seed=7):
     """Random-phase probe and the edge positions of test_hip_operators.problem(); psi is the current object, dpsi a
     direction, data = |fwd(truth)|^2 times noise."""
@@ -107,12 +102,11 @@ class Case:
     """One geometry: host problem, device operands, the float64 / float32 farplanes (made once) and a solver handle."""
 
     def __init__(self, g):
-        import torch
         import libtike.hipfft as pt
         self.g = g
         self.P = make_problem(*g)
         P = self.P
-        self.D = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
+        self.D = dev
         self.slv = pt.CGPtychoSolver(P["nscan"], P["nprb"], P["ndet"], P["ptheta"], P["nz"], P["n"])
         self.h = self.slv._h
         self.psi, self.dpsi, self.scan, self.prb = (self.D(P[k]) for k in ("psi", "dpsi", "scan", "prb"))
@@ -157,10 +151,6 @@ def set_stage(c, model, masked):
     nat.check(nat.set_option(c.h, b"model", nat.MODEL_POISSON_ML if model == "poisson_ml" else nat.MODEL_GAUSSIAN))
     nat.check(nat.set_mask(c.h, P_(c.mask) if masked else None, S_()))
     return (c.bad if masked else c.data), (c.P["bad"] if masked else c.P["data"]), (c.P["mask"] if masked else None)
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def check_sum(got, want, w32, scale, what):
@@ -357,27 +347,25 @@ def test_modes(case, M, model, masked):
 def test_compact_chunks_sum_to_the_full_search(geom, M, model):
     """compact_modes = M: fwd_cols_modes(into_b = 1, chunk) + linesearch_chunk over all M chunks (positions % M != 0, so
     the last chunk is short) adds up to the float64 search over all positions and modes."""
-    import torch
     import libtike.hipfft as pt
     nat, P_, S_ = nat_mod()
     P = make_problem(*geom)
     assert (P["ptheta"] * P["nscan"]) % M != 0
-    D = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
     rng = np.random.default_rng(M)
     prbs = [(P["prb"] * (0.7 ** k) * np.exp(2j * np.pi * rng.random(P["prb"].shape))).astype(np.complex64) for k in range(M)]
-    keep = [D(x) for x in prbs]
+    keep = [dev(x) for x in prbs]
     ptrs = (ctypes.c_void_p * M)(*[t.data_ptr() for t in keep])
     ab = np.array([0.8123, 0.6311])
     with pt.CGPtychoSolver(P["nscan"], P["nprb"], P["ndet"], P["ptheta"], P["nz"], P["n"]) as slv:
         h = slv._h
-        psi, dpsi, scan, data = D(P["psi"]), D(P["dpsi"]), D(P["scan"]), D(P["data"])
+        psi, dpsi, scan, data = dev(P["psi"]), dev(P["dpsi"]), dev(P["scan"]), dev(P["data"])
         nat.check(nat.set_option(h, b"model", nat.MODEL_POISSON_ML if model == "poisson_ml" else nat.MODEL_GAUSSIAN))
         nat.check(nat.set_option(h, b"compact_modes", M))
         nat.check(nat.cg_fwd_cols_modes(h, M, 0, P_(psi), P_(scan), ptrs, 0, 0, S_()))
         costs = zeros64(17)
         for ch in range(M):
             nat.check(nat.cg_fwd_cols_modes(h, M, 0, P_(dpsi), P_(scan), ptrs, 1, ch, S_()))
-            nat.check(nat.cg_linesearch_chunk(h, ch, P_(data), P_(D(ab)), GAMMA0, 16, P_(costs), S_()))
+            nat.check(nat.cg_linesearch_chunk(h, ch, P_(data), P_(dev(ab)), GAMMA0, 16, P_(costs), S_()))
         got = host(costs)
         nat.check(nat.set_option(h, b"compact_modes", 0))
     G = [cs.farplane(P["psi"], P["scan"], x, P["ndet"]) for x in prbs]

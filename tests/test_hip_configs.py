@@ -30,17 +30,9 @@ import pytest
 
 from oracle import cg_oracle as cg
 from libtike.hipfft import synthetic as syn
+from hip_common import dev, pt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
 
 
 from cg_cases import phase_screen   # noqa: E402  (shared with the CPU oracle tests)
@@ -164,7 +156,6 @@ def test_cg512_four_modes_tracks_the_oracle(pt):
 def _cfg2_device_problem(torch, seed=1234):
     """configs[1] at full size, on the device: 64 x 64 raster, 768^2 object, phase-screened probe."""
     p = syn.make_problem(64, 64, 8, 256, 256, seed=seed, nz=768, n=768)
-    dev = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
     probe = phase_screen(p["probe"][:, None], seed + 1)
     return p, dev(p["psi"]), dev(p["scan"]), dev(probe)
 
@@ -248,7 +239,6 @@ def test_cfg3_full_size_operator_properties(pt):
     four Hermite modes."""
     import torch
     p = syn.make_problem(64, 64, 8, 512, 512, seed=21, nz=1024, n=1024)
-    dev = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
     psi, scan = dev(p["psi"]), dev(p["scan"])
     modes = dev(syn.hermite_modes(512, 4))
     gen = torch.Generator(device="cuda").manual_seed(5)
@@ -280,7 +270,6 @@ def test_cfg4_shard_adjoint_identity_and_cg(pt):
     R1, R2 = 64, 512
     nz, n = syn.object_size_for(R1, R2, 8, 256)
     rng = np.random.default_rng(1)
-    dev = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
     psi = dev(syn.random_object(nz, n, rng))
     scan = dev(syn.raster_scan(R1, R2, 8, rng))
     prb = dev(phase_screen(syn.gaussian_probe(256), 3))
@@ -317,7 +306,6 @@ def test_cfg3_full_size_cg_properties(pt):
     import torch
     M, ndet = 4, 512
     p = syn.make_problem(64, 64, 8, ndet, ndet, seed=31, nz=1024, n=1024)
-    dev = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
     psi_true, scan = dev(p["psi"]), dev(p["scan"])
     modes = dev(phase_screen(syn.hermite_modes(ndet, M), 32))
     with pt.CGPtychoSolver(4096, ndet, ndet, 1, 1024, 1024) as slv:
@@ -388,7 +376,6 @@ def test_bench_problem_full_size_is_reproducible_and_descends(pt):
     reduction are order free), the logged cost never increases and no line search fails."""
     import torch
     p = syn.make_problem(64, 64, 8, 256, 256, seed=1234, nz=768, n=768)
-    dev = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
     psi_true, scan, probe = dev(p["psi"]), dev(p["scan"]), dev(p["probe"][:, None])
     with pt.CGPtychoSolver(4096, 256, 256, 1, 768, 768) as slv:
         slv.verbose, slv.log_every = False, 1

@@ -24,29 +24,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dpc_ref as ref  # noqa: E402
 import gauge_ref  # noqa: E402
+from hip_common import FACTOR, bound, dev, host, pt, same_bits  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
-
-FACTOR = 4
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import libtike.hipfft as pt
-    return pt
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 # ---- 1. moments -------------------------------------------------------------------------------------------------------------
@@ -144,7 +124,7 @@ def test_scan_map_bit_for_bit(pt, nz, n, nprb, nmodes, nscan, nval):
     e_dev, e32 = np.abs(w - r64).max() / r64.max(), np.abs(own - r64).max() / r64.max()
     print("scan map %s: weight err %.2e (float32 restatement %.2e), %d lit pixels" % ((nz, n, nprb, nmodes, nscan, nval),
                                                                                       e_dev, e32, (w > 0).sum()))
-    assert e_dev <= min(1e-4, max(FACTOR * e32, 1e-6))                                          # tests/test_hip_gauge.py
+    assert e_dev <= bound(e32, 1e-6, 1e-4)           # ILL_FLOOR, ILL_CAP of tests/test_hip_gauge.py
     assert (w > 0).any() and (w == 0).any() and np.isfinite(out).all()
     assert all((out[t][:, w[t] == 0] == 0).all() for t in range(ptheta))
     # with keep: the call on the kept subset, bit for bit, and the excluded positions may hold anything

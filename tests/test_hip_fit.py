@@ -15,19 +15,11 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fit_ref as ref  # noqa: E402
+from hip_common import dev, pt, same_bits  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 
 BOUND = 16 * ref.ULP
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
 
 
 _cases = {}
@@ -45,11 +37,6 @@ def case(name, plant=True):
     return _cases[key]
 
 
-def dev(x):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(x), device="cuda")
-
-
 def run_fit(pt, g, data, mask=None, ab=None, pixels=True):
     """``fit_frames`` on host arrays ``g [M, ...]``: the modes before the last one go through ``accumulate_intensity``."""
     inten = None
@@ -58,14 +45,6 @@ def run_fit(pt, g, data, mask=None, ab=None, pixels=True):
     out = pt.fit_frames(dev(data), dev(g[-1]), inten, None if mask is None else dev(mask), None if ab is None else dev(ab),
                         pixels=pixels)
     return out["frames"].cpu().numpy(), None if out["pixels"] is None else out["pixels"].cpu().numpy()
-
-
-def bits(x):
-    return np.ascontiguousarray(x).view(np.uint64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
 # ---- 1. against the float64 restatement -----------------------------------------------------------------------------------

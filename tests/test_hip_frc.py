@@ -16,28 +16,14 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import frc_ref as ref  # noqa: E402
+from hip_common import bound, dev, pt  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 
-FACTOR = 4
 SUM_FLOOR = 1e-5
 SUM_MAX = 1e-4
 FRC_TOL = 2e-4
 SHIFT_TOL = 0.01 + 1e-9
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
-
-
-def dev(x):
-    import torch
-    return torch.as_tensor(x, device="cuda")
 
 
 def lowpass(shape, rng, cutoff):
@@ -104,7 +90,7 @@ def test_frc_matches_the_restatement(pt, s, ptheta, complex_, taper, align):
     e_frc = np.abs(np.reshape(got["frc"], (ptheta, -1)) - r64["frc"]).max()
     print("S %d ptheta %d complex %s taper %.2f align %s: sums err %.2e (float32 restatement %.2e), frc err %.2e"
           % (s, ptheta, complex_, taper, align, e_dev, e32, e_frc))
-    assert e_dev <= min(SUM_MAX, max(FACTOR * e32, SUM_FLOOR)), (e_dev, e32)
+    assert e_dev <= bound(e32, SUM_FLOOR, SUM_MAX), (e_dev, e32)
     assert e_frc <= FRC_TOL
     assert np.array_equal(got["count"], r64["count"])
     assert np.allclose(got["frequency"], np.arange(s // 2 + 1) / s)

@@ -8,7 +8,7 @@ asks the model of that module, with the device's CU count, whether its case stil
 it goes through, so a device that cuts the runs differently cannot silently empty a case.  Expected values come from
 ``oracle.ptycho_oracle`` alone.
 
-Tolerances are the project's: ``REL_MAX`` / ``REL_L2`` of tests/test_hip_operators.py for operator outputs, ``check_array`` /
+Tolerances are the project's: ``REL_MAX`` / ``REL_L2`` of tests/hip_common.py for operator outputs, ``check_array`` /
 ``check_sum`` of tests/test_hip_cg_stages.py (``FACTOR`` x the float32 oracle's own error + floor) for the CG stages.
 ``pytest -m gpu``.
 """
@@ -22,18 +22,16 @@ from oracle import ptycho_oracle as op
 
 import cg_stages as cs
 import gatherwin_cases as gc
+from hip_common import FACTOR, REL_L2, REL_MAX, crand, host, rel_errors
 
 pytestmark = pytest.mark.gpu
 
-REL_MAX = 2e-5     # tests/test_hip_operators.py
-REL_L2 = 3e-6
 SUM_REL = 2e-6     # tests/test_hip_cg_stages.py
-FACTOR = 4
 TILE_KERNELS = ("k_fwd_tile", "k_adjprb_tile")
 
 
 @pytest.fixture(scope="module")
-def pt():
+def pt():   # not hip_common.pt: this one gives the shared cases and the device memory back when the module is done
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
@@ -50,17 +48,9 @@ def dev(x):
     return torch.as_tensor(np.array(x), device="cuda")   # a copy: the shared case arrays are read-only
 
 
-def host(x):
-    return x.detach().cpu().numpy()
-
-
 def n_cu():
     import torch
     return torch.cuda.get_device_properties(0).multi_processor_count   # what ptycho_create reads (hipDeviceProp_t)
-
-
-def crand(rng, shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
 
 
 def frozen(*arrays):
@@ -97,11 +87,6 @@ def want_adj_probe(name, which):
     return frozen(op.adj_probe(c["y"], c["scan"], c["psi"][which], c["nprb"], "double"))[0]
 
 
-def err(got, want):
-    d = np.abs(got.astype(np.complex128) - want)
-    return d.max() / np.abs(want).max(), np.sqrt((d ** 2).sum() / (np.abs(want) ** 2).sum())
-
-
 def check_events(name, launchers, chunk=0):
     """the case still reaches its events on this device, under every launcher it is there for"""
     for launch in launchers:
@@ -111,7 +96,7 @@ def check_events(name, launchers, chunk=0):
 
 
 def check_op(what, got, want):
-    e = err(got, want)
+    e = rel_errors(got, want)
     print("%s: rel_max %.3g (< %g) rel_l2 %.3g (< %g)" % (what, e[0], REL_MAX, e[1], REL_L2))
     assert e[0] < REL_MAX and e[1] < REL_L2, (what, e)
     return e
@@ -199,7 +184,7 @@ def test_split_and_unsplit_agree(pt, name):
             slv.set_split(split)
             out[split] = host(slv.fwd(psi, scan, prb)), host(slv.adj_probe(y, scan, psi))
     for i, what in enumerate(("fwd", "adj_probe")):
-        e = err(out[True][i], out[False][i].astype(np.complex128))
+        e = rel_errors(out[True][i], out[False][i].astype(np.complex128))
         print("%s %s split against un-split: rel_max %.3g (< %g)" % (name, what, e[0], 2 * REL_MAX))
         assert e[0] < 2 * REL_MAX, (what, e)
 

@@ -32,38 +32,15 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gauge_ref as ref  # noqa: E402
+from hip_common import FACTOR, REL_MAX, bound, dev, host, pt  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 
-FACTOR = 4
 ILL_FLOOR, ILL_CAP = 1e-6, 1e-4
 FIT_FLOOR, FIT_CAP = 1e-7, 1e-6
 APPLY_FLOOR, APPLY_CAP = 2.4e-7, 1e-3
 PLANT_G, PLANT_S = 2.0 ** -22, 2.0 ** -23
-ADJ_REL_MAX = 2e-5            # tests/test_hip_operators.py REL_MAX: adj against the oracle, relative to the maximum
 LIT_CAP = 1e-3                # at most 0.1 % of the pixels may sit within rounding of the lit threshold
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
-
-
-def dev(x):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(x), device="cuda")
-
-
-def host(x):
-    return x.detach().cpu().numpy()
-
-
-def bound(e32, floor, cap):
-    return min(cap, max(FACTOR * e32, floor))
 
 
 # ---- illumination -----------------------------------------------------------------------------------------------------
@@ -89,7 +66,7 @@ def ill_reference(name):
     return _ILL[name]
 
 
-def rel_max(got, want):
+def rel_max(got, want):     # not hip_common.rel_max: per plane, each relative to its own largest pixel
     return (np.abs(got.astype(np.float64) - want).max(axis=(-2, -1)) / np.abs(want).max(axis=(-2, -1))).max()
 
 
@@ -140,7 +117,7 @@ def test_illumination_is_the_diagonal_of_adj_fwd(pt, ndet):
             total += host(op.adj(op.fwd(ones, dev(scan), prb), dev(scan), prb)).real
     e = rel_max(ill, total)
     print("gauge operator identity ndet %d: err %.2e" % (ndet, e))
-    assert e <= ADJ_REL_MAX, e
+    assert e <= REL_MAX, e           # adj against the oracle, relative to the maximum
 
 
 # ---- fit ----------------------------------------------------------------------------------------------------------------

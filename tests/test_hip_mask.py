@@ -9,64 +9,13 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from cg_harness import (assert_ranks_match, check_run_batch_partitions, gpu_run, problem, same_run, solver,  # noqa: E402
+                        two_rank_run)
 from cg_reference import ReferenceSolver, detector_mask, random_mask  # noqa: E402
+from hip_common import dev, pt  # noqa: E402, F401
 import recon_metrics as rm  # noqa: E402
-from libtike.hipfft import synthetic as syn  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
-
-
-def problem(ndet, nmodes=1, seed=7, ny=6, step=6):
-    """setup() of test_hip_cg.py: phase-screened probe(s), consistent data."""
-    p = syn.make_problem(ny, ny, step, ndet, ndet, seed=seed)
-    probe = syn.hermite_modes(ndet, nmodes) if nmodes > 1 else p["probe"][:, None].copy()
-    rng = np.random.default_rng(seed + 100)
-    probe = (probe * np.exp(2j * np.pi * rng.random(probe.shape[-2:]))).astype(np.complex64)
-    ora = ReferenceSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
-    data = np.zeros((1, p["nscan"], ndet, ndet), np.float32)
-    for k in range(nmodes):
-        data += np.abs(ora.fwd(p["psi"], p["scan"], probe[:, k])) ** 2
-    return p, probe, data
-
-
-def solver(pt, p, ndet, path):
-    slv = pt.CGPtychoSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
-    slv.verbose, slv.log_every = False, 1
-    if path == "fused":
-        slv.native = False
-    elif path == "torch":
-        slv.fused = False
-        slv.set_deterministic(True)   # the torch loop's adjoints use float atomics unless told otherwise
-    return slv
-
-
-def gpu_run(slv, p, probe, data, mask=None, piter=4, recover=True, psi=None, **kw):
-    import torch
-    dev = torch.device("cuda", 0)
-    scan = torch.as_tensor(p["scan"].copy(), device=dev)
-    psi0 = np.ones_like(p["psi"]) if psi is None else psi
-    n0 = len(slv.history)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        res = slv.run(torch.as_tensor(data, device=dev), torch.as_tensor(psi0.copy(), device=dev), scan,
-                      torch.as_tensor(probe.copy(), device=dev), piter=piter, recover_prb=recover, mask=mask, **kw)
-    torch.cuda.synchronize()
-    return (res["psi"].cpu().numpy(), res["probe"].cpu().numpy(), scan.cpu().numpy(), list(slv.history[n0:]))
-
-
-def same_bits(a, b):
-    for x, y in zip(a[:3], b[:3]):
-        assert x.shape == y.shape and x.tobytes() == y.tobytes()
-    assert a[3] == b[3]
 
 
 # (name, ndet, nmodes, solver path): native single mode, the fused single-mode loop, the multi-mode loop, the torch loop
@@ -83,7 +32,7 @@ def test_all_ones_mask_is_no_mask_bitwise(pt, name, ndet, nmodes, path):
         want = gpu_run(slv, p, start, data)
     with solver(pt, p, ndet, path) as slv:
         got = gpu_run(slv, p, start, data, mask=np.ones((ndet, ndet), bool))
-    same_bits(got, want)
+    same_run(got, want)
 
 
 @pytest.mark.parametrize("garbage", [np.nan, -1.0, 1e30])
@@ -100,7 +49,7 @@ def test_unmeasured_data_is_ignored_bitwise(pt, name, ndet, nmodes, path, garbag
     with solver(pt, p, ndet, path) as slv:
         got = gpu_run(slv, p, start, bad, mask=torch.as_tensor(mask, device="cuda").float())
     assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all()
-    same_bits(got, want)
+    same_run(got, want)
 
 
 CASES = [(32, 1, False), (32, 1, True), (32, 2, True), (32, 2, False), (64, 1, True), (64, 2, True), (64, 1, False),
@@ -170,33 +119,13 @@ def test_no_state_leaks_between_runs(pt, path):
             gpu_run(slv, p, start, data, mask=mask, model="poisson")
         assert nat.get(slv._h, nat.GET_MASK) == 0
         got = gpu_run(slv, p, start, data)
-    same_bits(got, want)
+    same_run(got, want)
     assert masked[3] != want[3]
 
 
 def test_run_batch_partitions_with_a_mask(pt):
-    import torch
-    ndet = 64
-    p, probe, data = problem(ndet)
-    q, probe2, data2 = problem(ndet, seed=9)
-    assert p["nz"] == q["nz"] and p["n"] == q["n"]
-    mask = detector_mask(ndet)
-    start = np.concatenate([probe, probe2]).swapaxes(2, 3).copy()
-    D = np.concatenate([data, data2])
-    S = np.concatenate([p["scan"], q["scan"]])
-    psi = np.ones((2, p["nz"], p["n"]), np.complex64)
-    with pt.CGPtychoSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"]) as slv:
-        slv.verbose = False
-        got = slv.run_batch(D, psi, S.copy(), start.copy(), piter=4, recover_prb=True, mask=mask)
-    dev = torch.device("cuda", 0)
-    for k in range(2):
-        with pt.CGPtychoSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"]) as slv:
-            slv.verbose = False
-            res = slv.run(torch.as_tensor(D[k:k + 1].copy(), device=dev), torch.as_tensor(psi[k:k + 1].copy(), device=dev),
-                          torch.as_tensor(S[k:k + 1].copy(), device=dev), torch.as_tensor(start[k:k + 1].copy(), device=dev),
-                          piter=4, recover_prb=True, mask=torch.as_tensor(mask != 0, device=dev))
-        assert res["psi"].cpu().numpy().tobytes() == got["psi"][k:k + 1].tobytes()
-        assert res["probe"].cpu().numpy().tobytes() == got["probe"][k:k + 1].tobytes()
+    mask = detector_mask(64)
+    check_run_batch_partitions(pt, 64, 1, mask=mask, single_kw={"mask": dev(mask != 0)})
 
 
 def test_bad_masks_are_rejected(pt):
@@ -242,43 +171,9 @@ def test_masked_reconstruction_of_a_detector_with_dead_regions(pt):
     assert errs["masked"] < 1.5 * errs["complete"], errs
 
 
-def _run_rank(rank, world, port, out):
-    import torch
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        import libtike.hipfft as pt
-        from libtike.hipfft.distributed import shard_slice
-        p, probe, data = problem(32, seed=31)
-        sl = shard_slice(p["nscan"], rank, world)
-        dev = torch.device("cuda", 0)
-        with pt.CGPtychoSolver(sl.stop - sl.start, 32, 32, 1, p["nz"], p["n"], group=dist.group.WORLD) as slv:
-            slv.verbose, slv.log_every = False, 1
-            res = slv.run(torch.as_tensor(data[:, sl].copy(), device=dev),
-                          torch.ones((1, p["nz"], p["n"]), dtype=torch.complex64, device=dev),
-                          torch.as_tensor(p["scan"][:, sl].copy(), device=dev),
-                          torch.as_tensor(probe.copy(), device=dev), piter=5, recover_prb=True,
-                          mask=detector_mask(32))
-            out[rank] = (res["psi"].cpu().numpy(), res["probe"].cpu().numpy(), list(slv.history))
-    finally:
-        dist.destroy_process_group()
-
-
 def test_two_rank_masked_cg_matches_single_process(pt):
-    import torch
-    import torch.multiprocessing as mp
-    mgr = mp.Manager()
-    out = mgr.dict()
-    port = 29700 + ((os.getpid() + 1000) % 2000)
-    mp.spawn(_run_rank, args=(2, port, out), nprocs=2, join=True)
+    ranks = two_rank_run({"ndet": 32, "seed": 31}, {"piter": 5, "mask": detector_mask(32)}, salt=1000)
     p, probe, data = problem(32, seed=31)
     with solver(pt, p, 32, "default") as slv:
-        wpsi, wprb, _, hist = gpu_run(slv, p, probe, data, mask=detector_mask(32), piter=5)
-    for r in (0, 1):
-        psi, prb, h = out[r]
-        assert np.abs(psi - wpsi).max() < 2e-4 * np.abs(wpsi).max()
-        assert np.abs(prb - wprb).max() < 2e-4 * np.abs(wprb).max()
-        for a, b in zip(h, hist):
-            assert a[:3] == b[:3] and abs(a[3] - b[3]) <= 2e-4 * abs(b[3]), (a, b)
-    np.testing.assert_array_equal(out[0][0], out[1][0])
+        want = gpu_run(slv, p, probe, data, mask=detector_mask(32), piter=5)
+    assert_ranks_match(ranks, want)

@@ -11,34 +11,9 @@ import pytest
 
 from oracle import ptycho_oracle as op
 from libtike.hipfft import synthetic as syn
+from hip_common import REL_L2, REL_MAX, dev, host, pt, rel_errors  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-REL_MAX = 2e-5
-REL_L2 = 3e-6
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
-
-
-def dev(x):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(x), device="cuda")
-
-
-def host(x):
-    return x.detach().cpu().numpy()
-
-
-def err(got, want):
-    d = np.abs(got.astype(np.complex128) - want)
-    return d.max() / np.abs(want).max(), np.sqrt((d ** 2).sum() / (np.abs(want) ** 2).sum())
 
 
 def vdot(a, b):
@@ -104,13 +79,13 @@ def test_fwd_adj_adjprobe_match_oracle(pt, ndet, nprb, ny, nx, step, ntheta):
         for tile in ((True, False) if ndet <= 128 else (True,)):
             slv.set_tile(tile)
             g = host(slv.fwd(psi, scan, prb))
-            e = err(g, want_g)
+            e = rel_errors(g, want_g)
             assert e[0] < REL_MAX and e[1] < REL_L2, ("fwd", tile, e)
             if p["nscan"] >= 4:
                 assert np.all(g[0, 1] == 0)    # skipped position -> exact zeros
-            e = err(host(slv.adj(dev(y), scan, prb)), want_a)
+            e = rel_errors(host(slv.adj(dev(y), scan, prb)), want_a)
             assert e[0] < REL_MAX and e[1] < REL_L2, ("adj", tile, e)
-            e = err(host(slv.adj_probe(dev(y), scan, psi)), want_p)
+            e = rel_errors(host(slv.adj_probe(dev(y), scan, psi)), want_p)
             assert e[0] < REL_MAX and e[1] < REL_L2, ("adj_probe", tile, e)
 
 
@@ -136,7 +111,7 @@ def test_tile_kernels_equal_the_two_pass_kernels(pt, ndet, nprb, ny, nx):
         slv.profile(False)
     assert "k_fwd_tile" in ran and "k_adjprb_tile" in ran, ran      # the paths under test did run
     for name, a, b in zip(("fwd", "adj", "adj_probe"), got, ref):
-        e = err(a, b.astype(np.complex128))
+        e = rel_errors(a, b.astype(np.complex128))
         assert e[0] < 2e-5 and e[1] < 2e-6, (name, e)
     assert np.all(got[0][0, 1] == 0)        # skipped position -> exact zeros
 
@@ -154,8 +129,8 @@ def test_chunking_does_not_change_results(pt):
         slv.set_chunk(0)
         b0 = host(slv.adj_probe(dev(g0), scan, psi))
     np.testing.assert_array_equal(g0, g1)
-    assert err(a1, a0.astype(np.complex128))[0] < 1e-5      # atomics: order differs
-    assert err(b1, b0.astype(np.complex128))[0] < 1e-5
+    assert rel_errors(a1, a0.astype(np.complex128))[0] < 1e-5      # atomics: order differs
+    assert rel_errors(b1, b0.astype(np.complex128))[0] < 1e-5
 
 
 @pytest.mark.parametrize("ndet,nprb,ntheta", [(64, 64, 2), (128, 100, 1), (256, 256, 1)])
@@ -186,7 +161,7 @@ def test_object_adjoint_any_scan_order(pt, ndet, nprb, ntheta):
                         host(slv.adj_probe(dev(y), dev(scan), dev(psi)))))
     for got, got_f, got_p in res:
         for gg, ww in ((got, want), (got_f, want_f), (got_p, want_p)):
-            e = err(gg, ww)
+            e = rel_errors(gg, ww)
             assert e[0] < REL_MAX and e[1] < REL_L2, e
         assert np.all(got_f[0, 5] == 0)
 
@@ -275,7 +250,7 @@ def test_fft2_matches_numpy(pt):
             inplace = host(slv.fft2(xd, out=xd))
         wf = np.fft.fft2(x.astype(np.complex128))
         wb = np.fft.ifft2(x.astype(np.complex128)) * ndet * ndet
-        assert err(f, wf)[1] < REL_L2 and err(b, wb)[1] < REL_L2, (ndet, nb, tile)
+        assert rel_errors(f, wf)[1] < REL_L2 and rel_errors(b, wb)[1] < REL_L2, (ndet, nb, tile)
         np.testing.assert_array_equal(inplace, f)
 
 
@@ -301,7 +276,7 @@ def test_reference_adjoint_script(pt, model):
     a, b, c = vdot(psi0, t2), vdot(t1, t1), vdot(prb0[:, 0], t3)
     assert abs(a - b) / abs(a) < 1e-5 and abs(a - c) / abs(a) < 1e-5
     want = op.fwd(psi0, scan, prb0[:, 0], ndet, "double")
-    e = err(t1, want)
+    e = rel_errors(t1, want)
     assert e[0] < REL_MAX and e[1] < REL_L2
 
 

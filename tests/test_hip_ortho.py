@@ -1,40 +1,27 @@
 """Orthogonal probe modes on the GPU: ``libtike.hipfft.orthogonalize_modes`` (C ABI ``ptycho_orthogonalize_modes``)
 against the float64 NumPy reference of tests/ortho_modes.py, and ``CGPtychoSolver.run(..., ortho_prb=True)`` on the fused
 multi-mode loop and the torch loop against the reference loop of tests/cg_reference.py."""
+import functools
 import os
 import sys
-import warnings
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cg_harness as cg  # noqa: E402
 import ortho_modes as om  # noqa: E402
-from cg_cases import phase_screen  # noqa: E402
-from cg_reference import ReferenceSolver, detector_mask  # noqa: E402
-from test_hip_poisson import horizon  # noqa: E402  (its UNRESOLVED_STEP rule)
+from cg_harness import assert_ranks_match, check_run_batch_partitions, gpu_run, same_run, solver, two_rank_run  # noqa: E402
+from cg_reference import detector_mask  # noqa: E402
+from hip_common import dev, pt  # noqa: E402, F401
 import recon_metrics as rm  # noqa: E402
 from libtike.hipfft import synthetic as syn  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
-
-
-def dev(x):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(x), device=torch.device("cuda", 0))
-
-
 def max_rel(a, b):
-    return np.abs(a - b).max() / np.abs(b).max()
+    return np.abs(a - b).max() / np.abs(b).max()   # not hip_common.rel_max: the difference in the arrays' own precision
 
 
 # ---- the helper ---------------------------------------------------------------------------------------------------------
@@ -96,49 +83,8 @@ def test_summed_intensity_is_unchanged(pt):
 
 
 # ---- the CG loop ------------------------------------------------------------------------------------------------------------
-def problem(ndet, nmodes, seed=7, ny=6, step=6, dose=None):
-    """Non-orthogonal smooth modes under a phase screen; the noiseless intensities (dose=None) or Poisson-sampled data."""
-    p = syn.make_problem(ny, ny, step, ndet, ndet, seed=seed)
-    probe = phase_screen(om.mode_stack(ndet, nmodes, seed=seed), seed + 100)
-    ora = ReferenceSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
-    inten = np.zeros((1, p["nscan"], ndet, ndet), np.float32)
-    for k in range(nmodes):
-        inten += np.abs(ora.fwd(p["psi"], p["scan"], probe[:, k])) ** 2
-    if dose is None:
-        return p, probe, inten
-    rng = np.random.default_rng(seed + 200)
-    return p, probe, rng.poisson(inten * (dose / inten.max())).astype(np.float32)
-
-
-def solver(pt, p, ndet, path="default"):
-    slv = pt.CGPtychoSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
-    slv.verbose, slv.log_every = False, 1
-    if path == "torch":
-        slv.fused = False
-        slv.set_deterministic(True)
-    return slv
-
-
-def gpu_run(slv, p, probe, data, piter, **kw):
-    import torch
-    scan = dev(p["scan"].copy())
-    n0 = len(slv.history)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        res = slv.run(dev(data), dev(np.ones_like(p["psi"])), scan, dev(probe.copy()), piter=piter, recover_prb=True, **kw)
-    torch.cuda.synchronize()
-    return res["psi"].cpu().numpy(), res["probe"].cpu().numpy(), scan.cpu().numpy(), list(slv.history[n0:]), res
-
-
-def reference(p, start, data, piter, precision, **kw):
-    ndet = data.shape[-1]
-    ora = ReferenceSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"], precision=precision)
-    scan = p["scan"].copy()
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        res = ora.run(data.copy(), np.ones_like(p["psi"]), scan, start.copy(), piter=piter, recover_prb=True,
-                      ortho_prb=True, **kw)
-    return res["psi"], res["probe"], scan, ora.history
+#: non-orthogonal smooth modes (ortho_modes.mode_stack) under a phase screen
+problem = functools.partial(cg.problem, modes="mixed")
 
 
 def assert_orthogonal(probe):
@@ -149,31 +95,16 @@ def assert_orthogonal(probe):
         assert np.all(np.diff(d) <= 0), d
 
 
-def track(pt, p, start, data, path="default", piter=5, cost_rtol=1e-5, tol=5e-4, **kw):
-    """test_hip_poisson.track with ortho_prb=True: steps, logged costs, object and probe follow the float64 reference
-    up to the first iteration that the float32 and float64 references decide differently or by rounding."""
-    single = reference(p, start, data, piter, "single", **kw)[3]
-    double = reference(p, start, data, piter, "double", **kw)
-    split = horizon(single, double[3])
-    assert split >= 1, (single, double[3])
-    if split < piter:
-        double = reference(p, start, data, split, "double", **kw)
-    with solver(pt, p, data.shape[-1], path) as slv:
-        got = gpu_run(slv, p, start, data, split, ortho_prb=True, **kw)
-    assert len(got[3]) == split
-    mask = kw.get("mask")
-    dsum = float(np.where(mask != 0, data, 0).sum()) if mask is not None else float(data.sum())
-    for (i, gpsi, gprb, cost), (io, gpsi_o, gprb_o, cost_o) in zip(got[3], double[3]):
-        assert i == io
-        assert gpsi == gpsi_o and gprb == gprb_o, (split, got[3], double[3])
-        assert abs(cost - cost_o) <= cost_rtol * (abs(cost_o) + dsum), (i, cost, cost_o, dsum)
-    for k in (0, 1):
-        d = max_rel(got[k], double[k])
-        assert d < tol, (k, d)
+def assert_modes(got):
+    """The probe of a ``gpu_run`` is orthogonal, and ``mode_powers`` are its modes' powers."""
     assert_orthogonal(got[1])
     powers = got[4]["mode_powers"].cpu().numpy()
     assert max_rel(powers[0], np.diag(om.gram(got[1])[0]).real) < 1e-5
-    return split
+
+
+def track(pt, p, start, data, path="default", **kw):
+    """cg_harness.track with ortho_prb=True, and the modes stay orthogonal."""
+    return cg.track(pt, p, start, data, True, path, ortho_prb=True, extra=assert_modes, **kw)
 
 
 # (name, ndet, nmodes, path): the fused multi-mode loop at 128^2 and 256^2, the torch loop beyond 8 modes
@@ -204,32 +135,11 @@ def test_ortho_on_the_torch_loop(pt):
 
 
 def test_run_batch_partitions(pt):
-    import torch
-    ndet = 64
-    p, probe, data = problem(ndet, 3)
-    q, probe2, data2 = problem(ndet, 3, seed=9)
-    start = np.concatenate([probe, probe2])
-    D, S = np.concatenate([data, data2]), np.concatenate([p["scan"], q["scan"]])
-    psi = np.ones((2, p["nz"], p["n"]), np.complex64)
-    with solver(pt, p, ndet) as slv:
-        got = slv.run_batch(D, psi, S.copy(), start.copy(), piter=4, recover_prb=True, ortho_prb=True)
+    got = check_run_batch_partitions(pt, 64, 3, problem_kw={"modes": "mixed"}, swap=False, log_every=1, ortho_prb=True)
     assert_orthogonal(got["probe"])
-    for k in range(2):
-        with solver(pt, p, ndet) as slv:
-            res = slv.run(dev(D[k:k + 1]), dev(psi[k:k + 1]), dev(S[k:k + 1].copy()), dev(start[k:k + 1].copy()),
-                          piter=4, recover_prb=True, ortho_prb=True)
-        torch.cuda.synchronize()
-        assert res["psi"].cpu().numpy().tobytes() == got["psi"][k:k + 1].tobytes()
-        assert res["probe"].cpu().numpy().tobytes() == got["probe"][k:k + 1].tobytes()
 
 
 # ---- no effect when off ------------------------------------------------------------------------------------------------------
-def same_bits(a, b):
-    for x, y in zip(a[:3], b[:3]):
-        assert x.tobytes() == y.tobytes()
-    assert a[3] == b[3]
-
-
 @pytest.mark.parametrize("nmodes,path", [(2, "default"), (10, "torch"), (3, "torch")])
 def test_off_is_the_plain_loop_and_leaves_no_state(pt, nmodes, path):
     p, start, data = problem(64, nmodes)
@@ -239,8 +149,8 @@ def test_off_is_the_plain_loop_and_leaves_no_state(pt, nmodes, path):
         off = gpu_run(slv, p, start, data, 3, ortho_prb=False)
         on = gpu_run(slv, p, start, data, 3, ortho_prb=True)
         after = gpu_run(slv, p, start, data, 3)
-    same_bits(off, plain)
-    same_bits(after, plain)
+    same_run(off, plain)
+    same_run(after, plain)
     assert "mode_powers" not in plain[4] and "mode_powers" in on[4]
     assert on[1].tobytes() != plain[1].tobytes()
     assert_orthogonal(on[1])
@@ -252,7 +162,7 @@ def test_single_mode_and_no_probe_recovery_are_untouched(pt):
     with solver(pt, p, 64) as slv:
         a = gpu_run(slv, p, start, data, 3)
         b = gpu_run(slv, p, start, data, 3, ortho_prb=True)
-    same_bits(a, b)
+    same_run(a, b)
     p, start, data = problem(64, 3)
     outs = []
     for kw in ({}, {"ortho_prb": True}):
@@ -273,42 +183,14 @@ def test_more_than_16_modes_raise(pt):
 
 
 # ---- two ranks ----------------------------------------------------------------------------------------------------------------
-def _run_rank(rank, world, port, out):
-    import torch
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        import libtike.hipfft as pt
-        from libtike.hipfft.distributed import shard_slice
-        p, probe, data = problem(32, 3, seed=31)
-        sl = shard_slice(p["nscan"], rank, world)
-        with pt.CGPtychoSolver(sl.stop - sl.start, 32, 32, 1, p["nz"], p["n"], group=dist.group.WORLD) as slv:
-            slv.verbose, slv.log_every = False, 1
-            res = slv.run(dev(data[:, sl]), torch.ones((1, p["nz"], p["n"]), dtype=torch.complex64, device="cuda"),
-                          dev(p["scan"][:, sl].copy()), dev(probe.copy()), piter=1, recover_prb=True, ortho_prb=True)
-            out[rank] = (res["psi"].cpu().numpy(), res["probe"].cpu().numpy(), list(slv.history))
-    finally:
-        dist.destroy_process_group()
-
-
 def test_two_rank_ortho_matches_single_process(pt):
-    import torch.multiprocessing as mp
-    mgr = mp.Manager()
-    out = mgr.dict()
-    port = 29700 + ((os.getpid() + 1700) % 2000)
-    mp.spawn(_run_rank, args=(2, port, out), nprocs=2, join=True)
+    ranks = two_rank_run({"ndet": 32, "nmodes": 3, "seed": 31, "modes": "mixed"}, {"piter": 1, "ortho_prb": True}, salt=1700)
     p, probe, data = problem(32, 3, seed=31)
     with solver(pt, p, 32) as slv:
-        wpsi, wprb, _, hist, _ = gpu_run(slv, p, probe, data, 1, ortho_prb=True)
-    assert out[0][1].tobytes() == out[1][1].tobytes()       # every rank computes the same V
-    np.testing.assert_array_equal(out[0][0], out[1][0])
-    for r in (0, 1):
-        psi, prb, h = out[r]
-        assert max_rel(psi, wpsi) < 2e-4 and max_rel(prb, wprb) < 2e-4
-        for a, b in zip(h, hist):
-            assert a[:3] == b[:3] and abs(a[3] - b[3]) <= 2e-4 * abs(b[3]), (a, b)
-    assert_orthogonal(out[0][1])
+        want = gpu_run(slv, p, probe, data, 1, ortho_prb=True)
+    assert ranks[0][1].tobytes() == ranks[1][1].tobytes()       # every rank computes the same V
+    assert_ranks_match(ranks, want)
+    assert_orthogonal(ranks[0][1])
 
 
 # ---- the reference's 3-mode demo ----------------------------------------------------------------------------------------

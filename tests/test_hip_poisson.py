@@ -1,92 +1,32 @@
 """Poisson maximum-likelihood model of the CG reconstruction on the GPU: ``CGPtychoSolver.run(..., model="poisson_ml")``
 on every loop (native, host-driven fused, multi-mode, statement-by-statement torch), against the float64 NumPy reference
 of tests/cg_reference.py, with and without the detector mask."""
+import functools
 import os
 import sys
-import warnings
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from cg_cases import phase_screen  # noqa: E402
-from cg_reference import ReferenceSolver, detector_mask  # noqa: E402
+import cg_harness as cg  # noqa: E402
+from cg_harness import (assert_ranks_match, check_run_batch_partitions, intensity, reference, same_run,  # noqa: E402
+                        solver, two_rank_run)
+from cg_reference import detector_mask  # noqa: E402
+from hip_common import pt  # noqa: E402, F401
 import recon_metrics as rm  # noqa: E402
 from libtike.hipfft import synthetic as syn  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
+#: Poisson-sampled data unless a test says otherwise: 20 photons expected at the brightest pixel
+problem = functools.partial(cg.problem, dose=20.0)
+gpu_run = functools.partial(cg.gpu_run, model="poisson_ml")
 
 
-def intensity(p, probe):
-    ora = ReferenceSolver(p["nscan"], probe.shape[-1], probe.shape[-1], 1, p["nz"], p["n"])
-    inten = np.zeros((1, p["nscan"], probe.shape[-1], probe.shape[-1]), np.float32)
-    for k in range(probe.shape[1]):
-        inten += np.abs(ora.fwd(p["psi"], p["scan"], probe[:, k])) ** 2
-    return inten
-
-
-def problem(ndet, nmodes=1, seed=7, ny=6, step=6, dose=20.0):
-    """Phase-screened probe(s) (tests/cg_cases.py) and Poisson-sampled data: ``dose`` photons expected at the brightest
-    pixel.  dose=None: the noiseless intensities."""
-    p = syn.make_problem(ny, ny, step, ndet, ndet, seed=seed)
-    probe = syn.hermite_modes(ndet, nmodes) if nmodes > 1 else p["probe"][:, None].copy()
-    probe = phase_screen(probe, seed + 100)
-    inten = intensity(p, probe)
-    if dose is None:
-        return p, probe, inten
-    rng = np.random.default_rng(seed + 200)
-    return p, probe, rng.poisson(inten * (dose / inten.max())).astype(np.float32)
-
-
-def solver(pt, p, ndet, path):
-    slv = pt.CGPtychoSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"])
-    slv.verbose, slv.log_every = False, 1
-    if path == "fused":
-        slv.native = False
-    elif path == "torch":
-        slv.fused = False
-        slv.set_deterministic(True)   # the torch loop's adjoints use float atomics unless told otherwise
-    return slv
-
-
-def gpu_run(slv, p, probe, data, piter=4, recover=True, psi=None, model="poisson_ml", **kw):
-    import torch
-    dev = torch.device("cuda", 0)
-    scan = torch.as_tensor(p["scan"].copy(), device=dev)
-    psi0 = np.ones_like(p["psi"]) if psi is None else psi
-    n0 = len(slv.history)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        res = slv.run(torch.as_tensor(data, device=dev), torch.as_tensor(psi0.copy(), device=dev), scan,
-                      torch.as_tensor(probe.copy(), device=dev), piter=piter, recover_prb=recover, model=model, **kw)
-    torch.cuda.synchronize()
-    return (res["psi"].cpu().numpy(), res["probe"].cpu().numpy(), scan.cpu().numpy(), list(slv.history[n0:]))
-
-
-def reference(p, start, data, piter, recover, precision, psi=None, mask=None):
-    ndet = data.shape[-1]
-    ora = ReferenceSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"], precision=precision)
-    scan = p["scan"].copy()
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        res = ora.run(data.copy(), np.ones_like(p["psi"]) if psi is None else psi.copy(), scan, start.copy(),
-                      piter=piter, model="poisson_ml", recover_prb=recover, mask=mask)
-    return res["psi"], res["probe"], scan, ora.history
-
-
-def same_bits(a, b):
-    for x, y in zip(a[:3], b[:3]):
-        assert x.shape == y.shape and x.tobytes() == y.tobytes()
-    assert a[3] == b[3]
+def track(pt, p, start, data, recover, path, **kw):
+    """cg_harness.track on the Poisson model; the positions follow the reference to 1e-2 pixels."""
+    return cg.track(pt, p, start, data, recover, path, model="poisson_ml", scan_tol=1e-2, **kw)
 
 
 # (name, ndet, nmodes, recover, solver path, dose): the native single-mode loop at 256^2 with and without probe
@@ -96,49 +36,6 @@ TRACK = [("native256_prb", 256, 1, True, "default", 20.0), ("native256", 256, 1,
          ("fused64", 64, 1, True, "fused", 20.0), ("modes2_128", 128, 2, True, "default", 1000.0),
          ("modes4_512", 512, 4, True, "default", 1000.0), ("torch64", 64, 1, True, "torch", 20.0),
          ("torch100", 100, 1, True, "torch", 20.0)]
-
-
-#: an accepted step below this is decided at the float32 resolution of the cost: the second iteration's object search of
-#: every case here (after the probe rescale) accepts 1e-10 .. 2e-5, where f(trial) - f(p1) is a few float32 ulps of the
-#: summed cost, and the float32 reference, the GPU loops (float32 partial sums per thread) and a two-rank run each accept
-#: a different power of two there.  Measured: GPU 3.0e-8 / 1.5e-8 where the float64 reference accepts 1.5e-5 / 1.9e-6
-#: (2 and 4 modes); the float32 reference agreed with float64 there by its summation order.
-UNRESOLVED_STEP = 1e-4
-
-
-def horizon(single, double):
-    """Iterations that both references decide alike and on resolved line searches."""
-    for i, (a, b) in enumerate(zip(single, double)):
-        if a[1:3] != b[1:3] or 0.0 < b[1] < UNRESOLVED_STEP or 0.0 < b[2] < UNRESOLVED_STEP:
-            return i
-    return len(double)
-
-
-def track(pt, p, start, data, recover, path, mask=None, piter=5, cost_rtol=1e-5, tol=5e-4):
-    """Steps, logged costs, object, probe and positions follow the float64 reference up to -- not beyond -- the iteration
-    at which the float32 and float64 references themselves take different line-search decisions (or one of them is
-    decided by rounding, UNRESOLVED_STEP).  The logged cost is a sum of terms of both signs: its tolerance is relative to
-    |cost| + sum d."""
-    ndet = data.shape[-1]
-    single = reference(p, start, data, piter, recover, "single", mask=mask)[3]
-    double = reference(p, start, data, piter, recover, "double", mask=mask)
-    split = horizon(single, double[3])
-    assert split >= 1, (single, double[3])      # the case must say something
-    if split < piter:
-        double = reference(p, start, data, split, recover, "double", mask=mask)
-    with solver(pt, p, ndet, path) as slv:
-        got = gpu_run(slv, p, start, data, piter=split, recover=recover, mask=mask)
-    assert len(got[3]) == split
-    dsum = float(np.where(mask != 0, data, 0).sum()) if mask is not None else float(data.sum())
-    for (i, gpsi, gprb, cost), (io, gpsi_o, gprb_o, cost_o) in zip(got[3], double[3]):
-        assert i == io
-        assert gpsi == gpsi_o and gprb == gprb_o, (split, got[3], double[3])
-        assert abs(cost - cost_o) <= cost_rtol * (abs(cost_o) + dsum), (i, cost, cost_o, dsum)
-    for k in (0, 1):
-        d = np.abs(got[k] - double[k]).max() / np.abs(double[k]).max()
-        assert d < tol, (k, d)
-    assert np.abs(got[2] - double[2]).max() < 1e-2
-    return split
 
 
 @pytest.mark.parametrize("name,ndet,nmodes,recover,path,dose", TRACK, ids=[c[0] for c in TRACK])
@@ -159,7 +56,7 @@ def test_gradient_vanishes_at_the_truth(pt, path):
     p, probe, data = problem(ndet, 2 if path == "modes" else 1, dose=None)
     truth = p["psi"].astype(np.complex64)
     with solver(pt, p, ndet, "default" if path == "modes" else path) as slv:
-        psi, prb, _, hist = gpu_run(slv, p, probe, data, piter=1, recover=True, psi=truth)
+        psi, prb = gpu_run(slv, p, probe, data, piter=1, recover=True, psi=truth)[:2]
     assert np.abs(psi - truth).max() < 1e-4 * np.abs(truth).max(), np.abs(psi - truth).max()
     assert np.abs(prb - probe).max() < 1e-4 * np.abs(probe).max(), np.abs(prb - probe).max()
     # and the same start with gaussian-consistent but Poisson-sampled data moves (the check is not vacuous)
@@ -188,7 +85,7 @@ def test_deterministic_adjoint_with_dark_pixels(pt):
         with solver(pt, p, ndet, "default") as slv:
             slv.reproducible = det
             runs[det] = gpu_run(slv, p, probe, data, piter=2, recover=True, psi=truth)
-    want = reference(p, probe, data, 2, True, "double", psi=truth)
+    want = reference(p, probe, data, 2, "double", psi=truth, model="poisson_ml")
     for got in runs.values():
         assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all()
         assert [h[1:3] for h in got[3]] == [h[1:3] for h in want[3]], (got[3], want[3])
@@ -212,7 +109,7 @@ def test_all_ones_mask_is_no_mask_bitwise(pt, name, ndet, nmodes, path):
         want = gpu_run(slv, p, start, data)
     with solver(pt, p, ndet, path) as slv:
         got = gpu_run(slv, p, start, data, mask=np.ones((ndet, ndet), bool))
-    same_bits(got, want)
+    same_run(got, want)
 
 
 @pytest.mark.parametrize("garbage", [np.nan, -1.0, 1e30])
@@ -229,7 +126,7 @@ def test_unmeasured_data_is_ignored_bitwise(pt, name, ndet, nmodes, path, garbag
     with solver(pt, p, ndet, path) as slv:
         got = gpu_run(slv, p, start, bad, mask=torch.as_tensor(mask, device="cuda").float())
     assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all()
-    same_bits(got, want)
+    same_run(got, want)
 
 
 @pytest.mark.parametrize("ndet,nmodes,path", [(64, 1, "default"), (64, 2, "default"), (100, 1, "torch")])
@@ -268,7 +165,7 @@ def test_no_state_leaks_between_runs(pt, path):
         with pytest.raises(UnboundLocalError):      # model="poisson" stays broken like the reference's
             gpu_run(slv, p, start, data, model="poisson")
         got = gpu_run(slv, p, start, data, model="gaussian")
-    same_bits(got, want)
+    same_run(got, want)
     assert pml[3] != want[3]
 
 
@@ -293,75 +190,23 @@ def test_bitwise_reproducible_at_4096_positions(pt):
             res = slv.run(data, torch.ones((1, p["nz"], p["n"]), dtype=torch.complex64, device=dev), scan, prb.clone(),
                           piter=3, recover_prb=True, model="poisson_ml")
             runs.append((res["psi"].cpu().numpy(), res["probe"].cpu().numpy(), scan.cpu().numpy(), list(slv.history[n0:])))
-    same_bits(runs[0], runs[1])
+    same_run(runs[0], runs[1])
     assert all(np.isfinite(h[3]) for h in runs[0][3])
 
 
 def test_run_batch_partitions(pt):
-    import torch
-    ndet = 64
-    p, probe, data = problem(ndet)
-    q, probe2, data2 = problem(ndet, seed=9)
-    assert p["nz"] == q["nz"] and p["n"] == q["n"]
-    start = np.concatenate([probe, probe2]).swapaxes(2, 3).copy()
-    D = np.concatenate([data, data2])
-    S = np.concatenate([p["scan"], q["scan"]])
-    psi = np.ones((2, p["nz"], p["n"]), np.complex64)
-    with pt.CGPtychoSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"]) as slv:
-        slv.verbose = False
-        got = slv.run_batch(D, psi, S.copy(), start.copy(), piter=4, recover_prb=True, model="poisson_ml")
-    dev = torch.device("cuda", 0)
-    for k in range(2):
-        with pt.CGPtychoSolver(p["nscan"], ndet, ndet, 1, p["nz"], p["n"]) as slv:
-            slv.verbose = False
-            res = slv.run(torch.as_tensor(D[k:k + 1].copy(), device=dev), torch.as_tensor(psi[k:k + 1].copy(), device=dev),
-                          torch.as_tensor(S[k:k + 1].copy(), device=dev), torch.as_tensor(start[k:k + 1].copy(), device=dev),
-                          piter=4, recover_prb=True, model="poisson_ml")
-        assert res["psi"].cpu().numpy().tobytes() == got["psi"][k:k + 1].tobytes()
-        assert res["probe"].cpu().numpy().tobytes() == got["probe"][k:k + 1].tobytes()
-
-
-def _run_rank(rank, world, port, out):
-    import torch
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        import libtike.hipfft as pt
-        from libtike.hipfft.distributed import shard_slice
-        p, probe, data = problem(32, seed=31)
-        sl = shard_slice(p["nscan"], rank, world)
-        dev = torch.device("cuda", 0)
-        with pt.CGPtychoSolver(sl.stop - sl.start, 32, 32, 1, p["nz"], p["n"], group=dist.group.WORLD) as slv:
-            slv.verbose, slv.log_every = False, 1
-            res = slv.run(torch.as_tensor(data[:, sl].copy(), device=dev),
-                          torch.ones((1, p["nz"], p["n"]), dtype=torch.complex64, device=dev),
-                          torch.as_tensor(p["scan"][:, sl].copy(), device=dev),
-                          torch.as_tensor(probe.copy(), device=dev), piter=1, recover_prb=True, model="poisson_ml")
-            out[rank] = (res["psi"].cpu().numpy(), res["probe"].cpu().numpy(), list(slv.history))
-    finally:
-        dist.destroy_process_group()
+    check_run_batch_partitions(pt, 64, 1, problem_kw={"dose": 20.0}, model="poisson_ml")
 
 
 def test_two_rank_poisson_cg_matches_single_process(pt):
     """The all-reduced costs of both ranks are the Poisson sums: steps and logged costs are the single process's.  One
     iteration: the second one's object search accepts a step decided by rounding (UNRESOLVED_STEP), and two ranks sum
     in another order than one process."""
-    import torch.multiprocessing as mp
-    mgr = mp.Manager()
-    out = mgr.dict()
-    port = 29700 + ((os.getpid() + 1500) % 2000)
-    mp.spawn(_run_rank, args=(2, port, out), nprocs=2, join=True)
+    ranks = two_rank_run({"ndet": 32, "seed": 31, "dose": 20.0}, {"piter": 1, "model": "poisson_ml"}, salt=1500)
     p, probe, data = problem(32, seed=31)
     with solver(pt, p, 32, "default") as slv:
-        wpsi, wprb, _, hist = gpu_run(slv, p, probe, data, piter=1)
-    for r in (0, 1):
-        psi, prb, h = out[r]
-        assert np.abs(psi - wpsi).max() < 2e-4 * np.abs(wpsi).max()
-        assert np.abs(prb - wprb).max() < 2e-4 * np.abs(wprb).max()
-        for a, b in zip(h, hist):
-            assert a[:3] == b[:3] and abs(a[3] - b[3]) <= 2e-4 * abs(b[3]), (a, b)
-    np.testing.assert_array_equal(out[0][0], out[1][0])
+        want = gpu_run(slv, p, probe, data, piter=1)
+    assert_ranks_match(ranks, want)
 
 
 @pytest.mark.xfail(strict=True, reason="measured: poisson_ml object error 0.834 against 0.424 for gaussian (DESIGN.md 6)")

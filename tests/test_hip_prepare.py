@@ -12,17 +12,9 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import prepare_ref as ref  # noqa: E402
+from hip_common import dev, pt, same_bits  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
 
 
 _cases = {}
@@ -36,18 +28,8 @@ def case(name):
     return _cases[name]
 
 
-def dev(x):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(x), device="cuda")
-
-
-def host(out):
+def host(out):              # not hip_common.host: a dict of tensors, some of them None
     return {k: None if v is None else v.cpu().numpy() for k, v in out.items()}
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def assert_same_outputs(a, b):

@@ -7,30 +7,9 @@ import pytest
 from hypothesis import given, settings, strategies as st, HealthCheck
 
 from oracle import ptycho_oracle as op
+from hip_common import crand, dev, host, pt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
-
-
-def dev(x):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(x), device="cuda")
-
-
-def host(x):
-    return x.detach().cpu().numpy()
-
-
-def crand(rng, shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
 
 
 @st.composite
@@ -104,7 +83,6 @@ def test_cross_workgroup_sums_are_exact_and_repeatable(npos, ndet):
     scan = np.ascontiguousarray(p["scan"][:, :npos])
     rng = np.random.default_rng(npos)
     prb = (p["probe"] * np.exp(2j * np.pi * rng.random((ndet, ndet)))).astype(np.complex64)
-    dev = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda")
     with pt.CGPtychoSolver(npos, ndet, ndet, 1, p["nz"], p["n"]) as slv:
         psi, scan_d, prb_d = dev(p["psi"]), dev(scan), dev(prb)
         g = slv.fwd(psi, scan_d, prb_d)

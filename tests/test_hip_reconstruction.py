@@ -25,17 +25,9 @@ import recon_metrics as rm  # noqa: E402
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import recon_calib as rc  # noqa: E402  (scenario(): the two scripts' inputs from the fixtures)
+from hip_common import pt  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
 
 
 def reconstruct(pt, model, which, nscan, piter):

@@ -13,19 +13,11 @@ import numpy as np
 import pytest
 
 from oracle import cg_oracle as cg
+from hip_common import pt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 N, NZ, NPRB, NDET = 600, 276, 128, 128
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
 
 
 def scan_from(model, sel):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import cg_stages as cs
+from hip_common import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -43,11 +44,6 @@ def P():
 
 def solver(P, nb, ndet):
     return P.CGPtychoSolver(nb, ndet, ndet, 1, ndet + 8, ndet + 8)
-
-
-def dev(x):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(x), device="cuda")
 
 
 def packed(idx):

@@ -21,25 +21,16 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import resample_ref as ref  # noqa: E402
+from hip_common import bound, dev, host, pt  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 
-FACTOR, FLOOR, CAP = 4, 1e-6, 1e-4
+FLOOR, CAP = 1e-6, 1e-4
 SUM_TOL = 1e-12
 ORDERS = (0, 1, 2, 3, 4, 5)
 A = np.deg2rad(17.3)
 MATRIX = 0.83 * np.array([[np.cos(A), np.sin(A)], [-np.sin(A), np.cos(A)]])
 OFFSET = np.array([3.2, -1.7])
-
-
-def bound(e32):
-    return min(CAP, max(FACTOR * e32, FLOOR))
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import libtike.hipfft as pt
-    return pt
 
 
 @pytest.fixture(scope="module")
@@ -54,15 +45,7 @@ def L():
     return _native.SPLINE_SEGMENT
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def err(got, want):
+def err(got, want):         # not hip_common.rel_max: the difference is taken in the dtype of ``want``, real or complex
     return float(np.abs(got.astype(want.dtype) - want).max() / np.abs(want).max())
 
 
@@ -83,9 +66,9 @@ def check(name, got, fn):
     """``got`` against ``fn(dtype)`` in float64, bounded by the float32 run of the same ``fn``; prints the figures."""
     want, f32 = fn(np.float64), fn(np.float32)
     e_dev, e32 = err(got, want), err(f32, want)
-    print("resample %s: device %.2e, float32 restatement %.2e, bound %.2e" % (name, e_dev, e32, bound(e32)))
+    print("resample %s: device %.2e, float32 restatement %.2e, bound %.2e" % (name, e_dev, e32, bound(e32, FLOOR, CAP)))
     assert got.shape == want.shape
-    assert e_dev <= bound(e32), (name, e_dev, e32)
+    assert e_dev <= bound(e32, FLOOR, CAP), (name, e_dev, e32)
     return e_dev
 
 
@@ -162,7 +145,7 @@ def test_warp_tiles_outside_are_cval(rs, order):
     outside = want == 7.25
     assert outside[:32].all() and outside[:, 64:].all() and 0.05 < (~outside).mean() < 0.3
     assert (got[outside] == np.float32(7.25)).all()
-    assert err(got, want) <= bound(err(ref.warp(x, None, [-40.0, 20.0], (70, 90), order, cval=7.25, dtype=np.float32), want))
+    assert err(got, want) <= bound(err(ref.warp(x, None, [-40.0, 20.0], (70, 90), order, cval=7.25, dtype=np.float32), want), FLOOR, CAP)
 
 
 # ---- exactness ----------------------------------------------------------------------------------------------------------------
@@ -175,11 +158,11 @@ def test_exactness(pt, order):
     same = host(pt.warp(dev(x), order=order))
     e32 = err(ref.warp(x, order=order, dtype=np.float32), x.astype(np.complex128))
     print("resample identity order %d: device %.2e, float32 restatement %.2e" % (order, err(same, x.astype(np.complex128)), e32))
-    assert err(same, x.astype(np.complex128)) <= bound(e32)
+    assert err(same, x.astype(np.complex128)) <= bound(e32, FLOOR, CAP)
     z = host(pt.zoom(dev(x), 2, order=order, cval=np.nan))
     assert z.shape == (74, 106) and not np.isnan(z).any()                                 # the last row and column: never cval
     corners = (np.array([0, 0, -1, -1]), np.array([0, -1, 0, -1]))
-    assert np.abs(z[corners] - x[corners]).max() <= bound(e32) * np.abs(x).max()
+    assert np.abs(z[corners] - x[corners]).max() <= bound(e32, FLOOR, CAP) * np.abs(x).max()
 
 
 # ---- wrappers -----------------------------------------------------------------------------------------------------------------

@@ -11,7 +11,7 @@ The pass exists at ndet 256 only, so every case is 256 x 256.  What the cases ar
 (c) more positions than the forward grid has workgroups for, so that a workgroup walks several items: requests of the
     next item go out while LDS still holds the previous one.
 
-Tolerances are those of tests/test_hip_operators.py (float32 on the device, oracle in float64).
+Tolerances are the operators', ``REL_MAX`` / ``REL_L2`` of tests/hip_common.py (float32 on the device, oracle in float64).
 """
 import numpy as np
 import pytest
@@ -19,40 +19,16 @@ import pytest
 from oracle import ptycho_oracle as op
 from libtike.hipfft import synthetic as syn
 from gatherwin_cases import SPLIT_FWD_C, strip_range
+from hip_common import REL_L2, REL_MAX, dev, host, pt, rel_errors  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-REL_MAX = 2e-5
-REL_L2 = 3e-6
 NDET = 256
 FWD_WG_PER_CU = 32          # launch_rows_split<256, -1>: workgroups per CU in the grid (csrc/host_ops.hpp)
 
 
-@pytest.fixture(scope="module")
-def pt():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import libtike.hipfft as pt
-    return pt
-
-
-def dev(x):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(x), device="cuda")
-
-
-def host(x):
-    return x.detach().cpu().numpy()
-
-
-def err(got, want):
-    d = np.abs(got.astype(np.complex128) - want)
-    return d.max() / np.abs(want).max(), np.sqrt((d ** 2).sum() / (np.abs(want) ** 2).sum())
-
-
 def check(name, got, want):
-    e = err(got, np.asarray(want, dtype=np.complex128))
+    e = rel_errors(got, np.asarray(want, dtype=np.complex128))
     print("%s: rel max %.3e  rel l2 %.3e" % (name, e[0], e[1]))
     assert e[0] < REL_MAX and e[1] < REL_L2, (name, e)
 

@@ -22,31 +22,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import unwrap_ref as ref  # noqa: E402
+from hip_common import bound, dev, host, pt  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 
-FACTOR = 4
 FLOOR, CAP = 3e-5, 1e-3
 TWO_PI = 2.0 * np.pi
 SHAPE = (67, 129)
-
-
-def bound(d32):
-    return min(CAP, max(FACTOR * d32, FLOOR))
-
-
-@pytest.fixture(scope="module")
-def pt():
-    import libtike.hipfft as pt
-    return pt
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def centred(a, m=None):
@@ -158,7 +140,7 @@ def test_least_squares_solution_with_residues(pt):
     d32 = np.abs(centred(r32["phase"]) - centred(r64["phase"])).max()
     print("unwrap noisy least squares: device err %.2e rad (float32 restatement %.2e), %d iterations (%d, %d), %d residues"
           % (e_dev, d32, got["iterations"], r64["iterations"], r32["iterations"], got["residues"]))
-    assert e_dev <= bound(d32), (e_dev, d32)
+    assert e_dev <= bound(d32, FLOOR, CAP), (e_dev, d32)
     assert got["converged"] and got["residues"] == r64["residues"] > 0
 
 
@@ -190,7 +172,7 @@ def test_two_regions_each_up_to_its_own_constant(pt):
         d32 = np.ptp(r32["phase"].astype(np.float64)[:, cols] - truth[:, cols])
         d64 = np.ptp(r64["phase"].astype(np.float64)[:, cols] - truth[:, cols])
         print("unwrap two regions, columns %s: spread %.2e rad (float32 restatement %.2e, float64 %.2e)" % (cols, spread, d32, d64))
-        assert spread <= bound(d32), (spread, d32)
+        assert spread <= bound(d32, FLOOR, CAP), (spread, d32)
 
 
 # ---- 5. vortex pair ---------------------------------------------------------------------------------------------------------
@@ -279,6 +261,6 @@ def test_fix_gauge_then_unwrap(pt):
     d32 = np.abs(centred(r32["phase"], lit) - centred(r64["phase"], lit))[lit].max()
     err = np.abs(k - np.rint(k)).max() * TWO_PI
     print("unwrap after fix_gauge: %d iterations, distance from the planted phase %.2e rad (bound %.2e), span %.1f rad"
-          % (got["iterations"][0], err, bound(d32), np.ptp(out[lit])))
+          % (got["iterations"][0], err, bound(d32, FLOOR, CAP), np.ptp(out[lit])))
     assert np.ptp(np.rint(k)) == 0 and np.ptp(out[lit]) > TWO_PI
-    assert err <= bound(d32), (err, d32)
+    assert err <= bound(d32, FLOOR, CAP), (err, d32)
