@@ -7,7 +7,7 @@ import pytest
 from hypothesis import given, settings, strategies as st, HealthCheck
 
 from oracle import ptycho_oracle as op
-from hip_common import crand, dev, host, pt  # noqa: F401
+from hip_common import check_op, crand, dev, host, pt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -50,8 +50,8 @@ def test_linearity_adjointness_and_oracle(pt, g):
     r2 = np.vdot(bty.astype(np.complex128), prb1.astype(np.complex128))
     nrm = np.linalg.norm(g11) * np.linalg.norm(y) + 1e-20
     assert abs(lhs - r1) < 2e-6 * nrm and abs(lhs - r2) < 2e-6 * nrm
-    want = op.fwd(psi1, scan, prb1, ndet, "double")
-    assert np.abs(g11 - want).max() <= 2e-5 * (np.abs(want).max() + 1e-20)
+    check_op(g11, op.fwd(psi1, scan, prb1, ndet, "double"), op.fwd(psi1, scan, prb1, ndet, "single"),
+             "properties %d/%d x %d x %d seed %d fwd" % (ndet, nprb, ntheta, nscan, seed))
 
 
 def test_poisson_model_is_broken_like_the_reference(pt):

@@ -11,15 +11,16 @@ The pass exists at ndet 256 only, so every case is 256 x 256.  What the cases ar
 (c) more positions than the forward grid has workgroups for, so that a workgroup walks several items: requests of the
     next item go out while LDS still holds the previous one.
 
-Tolerances are the operators', ``REL_MAX`` / ``REL_L2`` of tests/hip_common.py (float32 on the device, oracle in float64).
+Tolerances are the operators': against the oracle ``check_op`` of tests/hip_common.py (FACTOR x the float32 oracle's own
+error), against the un-split path on the device the caps ``REL_MAX`` / ``REL_L2`` of that rule.
 """
 import numpy as np
 import pytest
 
-from oracle import ptycho_oracle as op
 from libtike.hipfft import synthetic as syn
 from gatherwin_cases import SPLIT_FWD_C, strip_range
-from hip_common import REL_L2, REL_MAX, dev, host, pt, rel_errors  # noqa: F401
+from operator_cases import oracles as oracles_at
+from hip_common import REL_L2, REL_MAX, check_op, dev, host, pt, rel_errors  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,6 +29,7 @@ FWD_WG_PER_CU = 32          # launch_rows_split<256, -1>: workgroups per CU in t
 
 
 def check(name, got, want):
+    """device against device (the un-split path)"""
     e = rel_errors(got, np.asarray(want, dtype=np.complex128))
     print("%s: rel max %.3e  rel l2 %.3e" % (name, e[0], e[1]))
     assert e[0] < REL_MAX and e[1] < REL_L2, (name, e)
@@ -41,6 +43,10 @@ def random_farplane(shape, seed):
 def phase_probe(nprb, seed):
     rng = np.random.default_rng(seed)
     return (syn.gaussian_probe(nprb) * np.exp(2j * np.pi * rng.random((1, nprb, nprb)))).astype(np.complex64)
+
+
+def oracles(psi, scan, prb, y, precision):
+    return oracles_at(psi, scan, prb, y, NDET, precision)
 
 
 def three_operators(slv, psi, scan, prb, y):
@@ -58,16 +64,15 @@ def test_order_and_skips(pt):
     assert np.all(np.diff(np.delete(scan[0, :, 0], 3)) < 0)
     psi_h, prb_h = syn.random_object(nz, n, rng), phase_probe(nprb, 22)
     y_h = random_farplane((1, 7, NDET, NDET), 23)
-    want = (op.fwd(psi_h, scan, prb_h, NDET, "double"), op.adj(y_h, scan, prb_h, nz, n, "double"),
-            op.adj_probe(y_h, scan, psi_h, nprb, "double"))
+    want, want32 = oracles(psi_h, scan, prb_h, y_h, "double"), oracles(psi_h, scan, prb_h, y_h, "single")
     with pt.PtychoCuFFT(7, nprb, NDET, 1, nz, n) as slv:
         psi, sc, prb, y = dev(psi_h), dev(scan), dev(prb_h), dev(y_h)
         got = three_operators(slv, psi, sc, prb, y)
         slv.set_split(False)
         ref = three_operators(slv, psi, sc, prb, y)
     assert np.all(got[0][0, 3] == 0)          # skipped position: exact zeros in every row
-    for name, g, w, r in zip(("fwd", "adj", "adj_probe"), got, want, ref):
-        check(name + " against the oracle", g, w)
+    for name, g, w, s, r in zip(("fwd", "adj", "adj_probe"), got, want, want32, ref):
+        check_op(g, w, s, "rows_split %s against the oracle" % name)
         check(name + " against the un-split path", g, r)
 
 
@@ -83,8 +88,7 @@ def test_column_limits_inside_the_row(pt):
     p["scan"][0, 5] = [-2.5, 3.0]                                         # skipped
     ns, nz, n = p["nscan"], p["nz"], p["n"]
     y_h = random_farplane((1, ns, NDET, NDET), 33)
-    want = (op.fwd(p["psi"], p["scan"], p["probe"], NDET, "double"), op.adj(y_h, p["scan"], p["probe"], nz, n, "double"),
-            op.adj_probe(y_h, p["scan"], p["psi"], nprb, "double"))
+    want, want32 = oracles(p["psi"], p["scan"], p["probe"], y_h, "double"), oracles(p["psi"], p["scan"], p["probe"], y_h, "single")
     import torch
     with pt.PtychoCuFFT(ns, nprb, NDET, 1, nz, n) as slv:
         psi, sc, prb, y = dev(p["psi"]), dev(p["scan"]), dev(p["probe"]), dev(y_h)
@@ -98,8 +102,8 @@ def test_column_limits_inside_the_row(pt):
     for o in outs[1:]:
         np.testing.assert_array_equal(o, outs[0])                         # the result does not depend on the sentinel
     assert np.all(outs[1][0, 5] == 0)
-    for name, g, w, r in zip(("fwd", "adj", "adj_probe"), got, want, ref):
-        check(name + " against the oracle", g, w)
+    for name, g, w, s, r in zip(("fwd", "adj", "adj_probe"), got, want, want32, ref):
+        check_op(g, w, s, "rows_split %s against the oracle" % name)
         check(name + " against the un-split path", g, r)
 
 
@@ -123,9 +127,7 @@ def test_several_items_per_workgroup(pt):
     sample = np.sort(rng.choice(ns, size=32, replace=False))
     sub = np.ascontiguousarray(p["scan"][:, sample])
     y_s = random_farplane((1, 32, NDET, NDET), 44)
-    want_g = op.fwd(p["psi"], sub, p["probe"], NDET, "double")
-    want_a = op.adj(y_s, sub, p["probe"], nz, n, "double")
-    want_p = op.adj_probe(y_s, sub, p["psi"], nprb, "double")
+    want, want32 = oracles(p["psi"], sub, p["probe"], y_s, "double"), oracles(p["psi"], sub, p["probe"], y_s, "single")
     with pt.PtychoCuFFT(ns, nprb, NDET, 1, nz, n) as slv:
         psi, sc, prb = dev(p["psi"]), dev(p["scan"]), dev(p["probe"])
         y = torch.zeros((1, ns, NDET, NDET), dtype=torch.complex64, device="cuda")
@@ -144,8 +146,7 @@ def test_several_items_per_workgroup(pt):
         print("fwd against the un-split path: worst position rel max %.3e  rel l2 %.3e" % (per_pos.max().item(), l2))
         assert per_pos.max().item() < REL_MAX and l2 < REL_L2, (int(per_pos.argmax()), per_pos.max().item(), l2)
         gs = host(g[:, dev(sample)])
-    check("fwd sample against the oracle", gs, want_g)
-    check("adj against the oracle", a, want_a)
-    check("adj_probe against the oracle", b, want_p)
+    for name, g, w, s in zip(("fwd sample", "adj", "adj_probe"), (gs, a, b), want, want32):
+        check_op(g, w, s, "rows_split several items %s against the oracle" % name)
     check("adj against the un-split path", af, afr)
     check("adj_probe against the un-split path", bf, bfr)
