@@ -89,6 +89,27 @@ int ptycho_adj(ptycho_handle h, void* f, const void* g, const void* scan,
 int ptycho_fft2(ptycho_handle h, void* dst, const void* src, size_t nbatch,
                 int dir, void* stream);
 
+/* Scan-position gradient (PtychoHIP.adj_scan, the backward of PtychoHIP.fwd_autograd; no counterpart in the reference):
+ * out (float32 [ptheta][nscan][2]) <- the derivative of Re <g, F Q f> with respect to scan, g held fixed, inside the
+ * interpolation cell that the position's truncation selects.  With (iy, ix) = trunc(scan) and (fy, fx) = scan - trunc(scan)
+ * on the float32 value, the taps f00 = f[iy+i][ix+j], f01 = f[iy+i][ix+j+1], f10 = f[iy+i+1][ix+j], f11 = f[iy+i+1][ix+j+1]
+ * (taps outside the object read 0), w = the centre nprb x nprb crop of the unnormalised inverse DFT of the position's tile
+ * of g and c = 1 / ndet:
+ *   out[..][0] = c Re sum_ij conj(w_ij) prb_ij ((f10 - f00)(1 - fx) + (f11 - f01) fx)
+ *   out[..][1] = c Re sum_ij conj(w_ij) prb_ij ((f01 - f00)(1 - fy) + (f11 - f10) fy)
+ * A position the operators skip (iy < 0 or ix < 0) gives exactly 0.0 twice; trunc(-0.3) = -0 is not skipped and has a
+ * negative fraction, as in ptycho_fwd.  Every element of out is written: the caller need not zero it.
+ * work: complex64 [work_tiles][ndet][ndet], work_tiles >= 1, not aliasing g; g is never modified.  The positions are taken in
+ * chunks of work_tiles: ptycho_fft2 (dir = +1) of the chunk into work, then one launch of one workgroup per position
+ * (csrc/k_scangrad.hpp), so every detector size of ptycho_fft2 works, the Bluestein sizes included.  Differences, weights and
+ * the product with the probe are float32, the sum is float64 in a fixed order with no atomics: the same inputs give the
+ * same bits, whatever work_tiles is.  Everything runs on `stream`, no host synchronisation; the position sort of the handle
+ * is neither used nor changed.
+ * PTYCHO_ERR_ARG, before any HIP call, for a null handle, a null out / g / f / scan / prb / work, work_tiles == 0, or
+ * work == g (PTYCHO_ERR_FREED for a handle after ptycho_free). */
+int ptycho_adj_scan(ptycho_handle h, float* out, const void* g, const void* f, const void* scan, const void* prb, void* work,
+                    size_t work_tiles, void* stream);
+
 /* Orthogonal incoherent probe modes (CGPtychoSolver.run(..., ortho_prb=True); no counterpart in the reference, whose
  * attempts are commented out at src/libtike/cufft/ptycho.py:414-419, 467-470).  Needs no handle.
  * prb (and dprb, gradprb0 when not null): complex64 [ptheta][nmodes][npix], npix = nprb^2, rotated in place.  Per angle t,

@@ -54,6 +54,7 @@
 #include "k_unwrap.hpp"
 #include "k_resample.hpp"
 #include "k_dpc.hpp"
+#include "k_scangrad.hpp"
 
 using namespace pty;
 
@@ -82,6 +83,7 @@ namespace {
 #include "host_propagate.hpp"
 #include "host_resample.hpp"
 #include "host_dpc.hpp"
+#include "host_scangrad.hpp"
 
 extern "C" {
 
@@ -345,6 +347,16 @@ int ptycho_fft2(ptycho_handle h, void* dst, const void* src, size_t nbatch, int 
     hipStream_t st = (hipStream_t)stream;
     if (h->bs_m) { PTY_DISPATCH_POW2(h->bs_m, (do_fft2_generic<NN>(h, (c32*)dst, (const c32*)src, (long long)nbatch, dir, st))); }
     PTY_DISPATCH(h->ge.ndet, (do_fft2<NN>(h, (c32*)dst, (const c32*)src, (long long)nbatch, dir, st)));
+}
+
+// ---- scan-position gradient (k_scangrad.hpp, PtychoHIP.adj_scan / fwd_autograd) -----------------------------------------
+int ptycho_adj_scan(ptycho_handle h, float* out, const void* g, const void* f, const void* scan, const void* prb, void* work,
+                    size_t work_tiles, void* stream) {
+    if (int rc = check_args(h, out, g, f, scan, prb, work)) return rc;
+    if (work_tiles == 0) return fail(PTYCHO_ERR_ARG, "work_tiles must be positive");
+    if (work == g) return fail(PTYCHO_ERR_ARG, "work must not be g");
+    return do_adj_scan(h, out, (const c32*)g, (const c32*)f, (const float*)scan, (const c32*)prb, (c32*)work, work_tiles,
+                       (hipStream_t)stream);
 }
 
 // ---- CG stages, one probe -----------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("PTYCHO_HIP_LIB") or os.path.join(_HERE, "libptychohip
 
 #: every symbol ``include/ptycho_hip.h`` declares
 SYMBOLS = ("ptycho_create", "ptycho_free", "ptycho_destroy", "ptycho_get",
-           "ptycho_fwd", "ptycho_adj", "ptycho_fft2", "ptycho_set_option",
+           "ptycho_fwd", "ptycho_adj", "ptycho_fft2", "ptycho_adj_scan", "ptycho_set_option",
            "ptycho_profile", "ptycho_profile_read",
            "ptycho_cg_fwd_cols", "ptycho_cg_stats", "ptycho_cg_project",
            "ptycho_cg_adj_cols", "ptycho_cg_linesearch",
@@ -65,6 +65,8 @@ get = _sig("ptycho_get", _ll, _vp, _i)
 fwd = _sig("ptycho_fwd", _i, _vp, _vp, _vp, _vp, _vp, _vp)
 adj = _sig("ptycho_adj", _i, _vp, _vp, _vp, _vp, _vp, _i, _vp)
 fft2 = _sig("ptycho_fft2", _i, _vp, _vp, _vp, _sz, _i, _vp)
+#: h, out, g, f, scan, prb, work, work_tiles, stream
+adj_scan = _sig("ptycho_adj_scan", _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp)
 set_option = _sig("ptycho_set_option", _i, _vp, ctypes.c_char_p, _ll)
 cg_fwd_cols = _sig("ptycho_cg_fwd_cols", _i, _vp, _i, _vp, _vp, _vp, _vp)
 cg_stats = _sig("ptycho_cg_stats", _i, _vp, _i, _vp, _vp, _vp)

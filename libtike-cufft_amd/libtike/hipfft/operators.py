@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .autograd import FwdFunction
 
 
 class TorchArrayModule:
@@ -245,6 +246,42 @@ class PtychoHIP:
         self._note_scan(scan)
         nat.check(nat.adj(self._h, _ptr(psi), _ptr(farplane), _ptr(scan), _ptr(probe), 1, _stream()))
         return probe
+
+    def adj_scan(self, farplane, scan, psi, probe, out=None, chunk=None):
+        """Scan-position gradient: float32 ``[ptheta, nscan, 2]``, the derivative of ``Re <farplane, fwd(psi, scan, probe)>``
+        with respect to ``scan`` with ``farplane`` held fixed, inside the interpolation cell of every position (at an
+        integer coordinate: of the cell that the truncation selects).  Skipped positions (integer part < 0) give 0.0.
+
+        ``out``: optional result tensor, every element is written.  ``chunk``: positions per inverse transform; the work
+        buffer (``chunk`` detector tiles, from torch's allocator) is at most 256 MiB when ``chunk`` is ``None``.  The result
+        does not depend on ``chunk``, and two calls give the same bits."""
+        farplane = self._operand(farplane, torch.complex64, (self.ptheta, self.nscan, self.ndet, self.ndet), "farplane")
+        scan = self._operand(scan, torch.float32, (self.ptheta, self.nscan, 2), "scan")
+        psi = self._operand(psi, torch.complex64, (self.ptheta, self.nz, self.n), "psi")
+        probe = self._operand(probe, torch.complex64, (self.ptheta, self.nprb, self.nprb), "probe")
+        if out is None:
+            grad = torch.empty((self.ptheta, self.nscan, 2), dtype=torch.float32, device=farplane.device)
+        else:
+            grad = self._operand(out, torch.float32, (self.ptheta, self.nscan, 2), "out")
+            assert grad is out, "out must be contiguous"
+        total = self.ptheta * self.nscan
+        if chunk is None:
+            chunk = max(1, (256 << 20) // (self.ndet * self.ndet * 8))
+        elif int(chunk) < 1:
+            raise ValueError("chunk must be at least 1, got %r" % (chunk,))
+        chunk = min(int(chunk), total)
+        work = torch.empty((chunk, self.ndet, self.ndet), dtype=torch.complex64, device=farplane.device)
+        self._note_scan(scan)
+        nat.check(nat.adj_scan(self._h, _ptr(grad), _ptr(farplane), _ptr(psi), _ptr(scan), _ptr(probe), _ptr(work), chunk,
+                               _stream()))
+        return grad
+
+    def fwd_autograd(self, psi, scan, probe):
+        """``fwd`` with a ``torch.autograd`` graph: the same arguments and the same result bits; ``backward`` gives the
+        gradients of a real loss for ``psi`` (``adj``), ``probe`` (``adj_probe``) and ``scan`` (``adj_scan``, float32),
+        only those that require one.  Several probe modes: sum the intensities of ``fwd_autograd(psi, scan, probe[:, k])``;
+        autograd adds the gradients up."""
+        return FwdFunction.apply(self, psi, scan, probe)
 
     def fft2(self, x, inverse=False, out=None):
         """Unnormalised batched 2-D DFT of ``[..., ndet, ndet]`` complex64 tiles
